@@ -15,6 +15,16 @@ device-side initial draw inside the wall time as well; file I/O excluded.
 When --gpus N > 1 is given without a torch.distributed environment (WORLD_SIZE unset) the script re-launches itself under
 `python -m torch.distributed.run --nproc-per-node N`; it refuses to run with a world size other than N.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs) and the
+line.  --full adds everything that takes runs of its own: the roofline of the dominant kernel (one more, profiled run), the CPU
+baseline (the C port of the reference on the host's cores; --no-cpu skips it) and, at N > 1, the same workload on rank 0's GPU
+alone (--no-ref skips it).
+--dump-outputs DIR writes what the last timed step computed, as the package's smc() hands it to a caller, to DIR/<name>.npy
+(float64; rank 0's shard at N > 1): the final cloud (n x (n_para + 5), column-major like Engine.download_cloud), the stage
+records (tempering_schedule, ess, c, accept, resampled), the weight history (incremental_weights, normalized_weights: n x stages)
+when it is stored, and the scalars logmdd, n_stages, resamples.  Clouds above DUMP_CLOUD_BYTES and histories above
+DUMP_HISTORY_ROWS rows are a fixed, seeded sample of rows (their indices in cloud_rows / history_rows), 64 MB at most in all.
 """
 import argparse
 import json
@@ -36,6 +46,13 @@ N_TOTAL_SHARDED = 1_000_000    # config 3 (--gpus N > 1): this many particles IN
 RUN_KW = dict(use_fixed_schedule=False, tempering_target=0.97, n_phi=300, lam=2.1, resampling_method="systematic",
               n_blocks=1, n_mh_steps=1, alpha=1.0, c=0.5, target=0.25, threshold_ratio=0.5)
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+# --dump-outputs: at most this many bytes of cloud rows and this many rows of the two weight histories (1500 stages at most:
+# 2 x 1024 x 1500 x 8 bytes = 24.6 MB), beyond that a sample of rows drawn with DUMP_SEED.  With the row indices (8 bytes per
+# row, at most 24 MiB / 48 of them) and the stage records a dump stays below 55 MB.
+DUMP_CLOUD_BYTES = 24 << 20
+DUMP_HISTORY_ROWS = 1024
+DUMP_HISTORY_MAX_DOWNLOAD = 4 << 30     # larger histories are not downloaded at all (the library copies them whole)
+DUMP_SEED = 20240917
 
 
 def mutate_bytes_per_particle(d):
@@ -87,20 +104,59 @@ def resolve_world(n_gpus, environ):
     return (world, False)
 
 
-def main():
-    # A collective that never completes (a rank died, a transport misbehaves) must not hold the GPUs until somebody's outer limit
-    # fires: dump the Python stacks and exit after SMCMI_BENCH_WATCHDOG seconds (default 15 min; the default run takes ~1 min).
-    import faulthandler
+def _sample_rows(n, cap):
+    """None (every row) when n <= cap, else `cap` sorted row indices drawn with DUMP_SEED: the same rows in every run."""
+    import numpy as np
 
-    faulthandler.dump_traceback_later(int(os.environ.get("SMCMI_BENCH_WATCHDOG", "900")), exit=True)
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+
+
+def dump_outputs(eng, res, out_dir, history):
+    """--dump-outputs: what the timed path's last step left in the handle `eng` (its result dict `res`), as smc() hands it to a caller
+    (the module docstring lists the files).  Every array is float64."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    cloud = eng.download_cloud()
+    rows = _sample_rows(cloud.shape[0], max(DUMP_CLOUD_BYTES // (8 * cloud.shape[1]), 1))
+    arrays["cloud"] = cloud if rows is None else cloud[rows]
+    if rows is not None:
+        arrays["cloud_rows"] = rows
+    del cloud
+    k = int(res["n_stages"])
+    rec = eng.stage_records(k)
+    arrays.update(tempering_schedule=rec["schedule"], ess=rec["ess"], c=rec["c_hist"], accept=rec["accept_hist"], resampled=rec["resampled"])
+    if history:
+        if 2 * 8 * eng.n * max(k, eng.stages_held()) <= DUMP_HISTORY_MAX_DOWNLOAD:
+            w, W = eng.history(k)
+            hrows = _sample_rows(w.shape[0], DUMP_HISTORY_ROWS)
+            arrays["incremental_weights"] = w if hrows is None else w[hrows]
+            arrays["normalized_weights"] = W if hrows is None else W[hrows]
+            if hrows is not None:
+                arrays["history_rows"] = hrows
+            del w, W
+        else:
+            sys.stderr.write("bench.py: --dump-outputs: the weight history of %d rows x %d stages is too large to download: not written\n" % (eng.n, k))
+    arrays.update(logmdd=res["logmdd"], n_stages=res["n_stages"], resamples=res["resamples"])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--nparts", type=int, default=0, help="particles in total (default: 100 000 at --gpus 1, 1 000 000 at --gpus N > 1)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU-oracle baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: roofline, CPU baseline, single-GPU reference at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU-oracle baseline leg")
     ap.add_argument("--no-history", action="store_true")
-    ap.add_argument("--no-ref", action="store_true", help="--gpus N > 1: skip the single-GPU run of the same workload on rank 0")
+    ap.add_argument("--no-ref", action="store_true", help="--full, --gpus N > 1: skip the single-GPU run of the same workload on rank 0")
     ap.add_argument("--workload", default="gauss10", choices=["gauss10", "capm", "kalman"],
                     help="gauss10 = BASELINE config 2 (the bench line); capm = config 4 (examples/capm_model, 3 MH steps, fixed schedule); kalman = config 5 (13-parameter state-space model, Kalman-filter likelihood, old + new data)")
     ap.add_argument("--solver-passes", type=int, default=0)
@@ -108,7 +164,19 @@ def main():
     ap.add_argument("--phi-rtol", type=float, default=0.0, help="adaptive-phi root tolerance (0 = library default)")
     ap.add_argument("--alpha", type=float, default=None, help="mixture weight of the proposal (default: the workload's own)")
     ap.add_argument("--n-blocks", type=int, default=None, help="random parameter blocks per MH step (default: the workload's own)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def main():
+    # A collective that never completes (a rank died, a transport misbehaves) must not hold the GPUs until somebody's outer limit
+    # fires: dump the Python stacks and exit after SMCMI_BENCH_WATCHDOG seconds (default 15 min; the default run takes ~1 min).
+    import faulthandler
+
+    faulthandler.dump_traceback_later(int(os.environ.get("SMCMI_BENCH_WATCHDOG", "900")), exit=True)
+    args = parse_args(sys.argv[1:])
 
     world, must_spawn = resolve_world(args.gpus, os.environ)
     if must_spawn:
@@ -203,7 +271,8 @@ def main():
         else:
             eng.set_model(spec)
             eng.init_from_prior()
-            P0 = eng.download_cloud()            # pristine initial cloud (prior draws + log-likelihoods): the CPU baseline starts from it
+            # pristine initial cloud (prior draws + log-likelihoods): the CPU baseline (--full) starts from it
+            P0 = eng.download_cloud() if args.full else None
 
             def reset():
                 # every step is a whole job: the device draws the initial cloud again (same seed, same Philox streams => the same
@@ -311,6 +380,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = n_total * stages / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, last, args.dump_outputs, history=not args.no_history)
 
     out = {
         "metric": "particle-stages/sec", "value": value, "unit": "particle-stages/s", "n_gpus": world,
@@ -336,14 +407,18 @@ def main():
         "shift_fallback_stage": last.get("shift_fallback_stage", 0),
         "logmdd_exact": models.gauss_logmdd(D) if args.workload == "gauss10" else None, "solver_passes_per_stage": last.get("solver_passes", 0) / max(last["n_stages"] - 1, 1),
     }
+    # whole-stage algorithmic bytes: 24d+96 per particle-stage, +16d+104 on resample stages
+    stage_bytes = n_total * ((24 * D + 96) * (last["n_stages"] - 1) + (16 * D + 104) * last["resamples"])
+    out["stage_gbs"] = stage_bytes * args.steps / dt / 1e9
 
+    # ---- --full: the figures that take runs of their own (roofline, CPU baseline, single-GPU reference)
     sharded = world > 1 or force_sharded
     prof = None
-    if sharded:
+    if sharded and args.full:
         # every rank takes part in the profiled run (it holds collectives); rank 0 reports its own GPU's kernel
         prof = one_step(profile=True)
         barrier()
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (mutation): HIP events around every k_mutate launch of one more
         # identical run on the engine's stream (use_graph = 2), algorithmic bytes / mean duration.  Multi-GPU lines quote the
         # kernel of rank 0's GPU on its shard (n_local particles): per-GPU figures, like `peak`.
@@ -456,9 +531,6 @@ def main():
                                "pmc_file": os.path.relpath(pmc_file, ROOT) if pmc_file else None, "flops_per_launch": flops,
                                "mean_launch_us": 1e3 * mean_ms, "launches": nl,
                                "filter_steps_per_proposal": steps, "old_data_prefix_shared": shared}
-        # whole-stage algorithmic bytes: 24d+96 per particle-stage, +16d+104 on resample stages
-        stage_bytes = n_total * ((24 * D + 96) * (last["n_stages"] - 1) + (16 * D + 104) * last["resamples"])
-        out["stage_gbs"] = stage_bytes * args.steps / dt / 1e9
         if not args.no_cpu and not sharded:          # CPU baseline: rank 0 at N = 1 only
             # Two variants of the CPU port on all host cores (BASELINE.md §3 / SURVEY §8d-ii), each on the full workload once
             # (same cloud, same Philox seed):

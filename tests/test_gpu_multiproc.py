@@ -193,7 +193,8 @@ def test_bench_py_with_several_ranks_on_one_gpu(world, comm):
         subprocess.check_call(["make", "-C", fake, "libfake_rccl.so"], stdout=subprocess.DEVNULL)
         env["SMCMI_RCCL_PATH"] = os.path.join(fake, "libfake_rccl.so")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--nparts", "65536", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-history"],
+                        os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--nparts", "65536", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-history",
+                        "--full"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

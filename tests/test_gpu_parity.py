@@ -700,14 +700,15 @@ def test_c_abi_example_matches_the_python_binding(tmp_path):
 
 
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the fields the driver reads, `roofline` included (small cloud, no CPU leg)."""
+    """bench.py --full prints ONE JSON line with the fields the driver reads, `roofline` included (small cloud, no CPU leg)."""
     import json
     import os
     import subprocess
     import sys
 
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--nparts", "20000", "--no-cpu"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--nparts", "20000", "--no-cpu",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -729,6 +730,53 @@ def test_bench_line_contract():
     assert 0 < r["floor_us"] <= r["mean_stage_us"] and 0 < r["cus_occupied"] <= 256 and r["hand_overs_per_stage"] == 2
     assert r["mutation_kernel_outside_segments"]["launches"] == 0          # every mutation of this run ran inside segments
     assert d["segment_state"] == 1 and d["segment_timeouts"] == 0 and d["segment_blocks"] == r["cus_occupied"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line without the figures that take runs of their own, and
+    --dump-outputs writes what its last timed step computed: the same cloud, stage records and log-MDD, bit for bit, as one
+    Engine.run of the same workload on the same seed (every step re-draws the cloud on the device)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from smc_jl_amd import Engine
+
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n, out = 20000, tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--nparts", str(n),
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    for k in ("roofline", "cpu_baseline", "single_gpu_same_workload"):
+        assert k not in d, k
+    got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    e = Engine(n, 10, seed=1, max_stages=1500, store_history=True)
+    e.set_model(models.gauss_spec(10))
+    e.init_from_prior()
+    g = e.run(**bench.RUN_KW)
+    rec = e.stage_records(g["n_stages"])
+    w, W = e.history(g["n_stages"])
+    P = e.download_cloud()
+    e.close()
+    assert got["n_stages"] == g["n_stages"] == d["n_stages"] and got["resamples"] == g["resamples"]
+    assert got["logmdd"] == g["logmdd"] == d["logmdd_gpu"]
+    np.testing.assert_array_equal(got["cloud"], P)
+    for name, key in (("tempering_schedule", "schedule"), ("ess", "ess"), ("c", "c_hist"), ("accept", "accept_hist"), ("resampled", "resampled")):
+        np.testing.assert_array_equal(got[name], rec[key], err_msg=name)
+    rows = got["history_rows"].astype(np.int64)                    # 20 000 rows > DUMP_HISTORY_ROWS: a seeded sample of them
+    assert rows.size == bench.DUMP_HISTORY_ROWS
+    np.testing.assert_array_equal(got["incremental_weights"], w[rows])
+    np.testing.assert_array_equal(got["normalized_weights"], W[rows])
 
 
 def test_device_proposal_densities_against_the_reference_fixture(orc, golden):

@@ -293,7 +293,7 @@ def test_two_rank_rccl_run_when_two_gpus_are_visible():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--nparts", "80000",
-                        "--no-cpu"], env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
+                        "--no-cpu", "--full"], env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["n_parts_per_gpu"] == 40000

@@ -2,7 +2,7 @@
 # development: the bench lines of two builds of the library side by side.  usage: bash tools/ab_lib.sh <other .so> [workload nparts ...]
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 OTHER=$1; shift
-run() { env "$@" timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu --workload $WL --nparts $N 2>/dev/null | python -c "
+run() { env "$@" timeout 600 python bench.py --full --steps 8 --warmup 2 --no-cpu --workload $WL --nparts $N 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

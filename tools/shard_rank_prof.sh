@@ -20,9 +20,9 @@ for N in ${@:-250000 500000}; do
   export SMCMI_E2_NB1=$(( (N / 8 + 1023) / 1024 ))
   for mb in 2 0; do
     echo "== N=$N SMCMI_MAILBOX=$mb SMCMI_E2_NB1=$SMCMI_E2_NB1 ${EXTRA_ENV}"
-    SMCMI_MAILBOX=$mb timeout 300 python bench.py --gpus 1 --steps 5 --warmup 1 --no-cpu --no-history --nparts $N 2>/dev/null | grep '^{' | tee $OUT/bench_n${N}_mb$mb.json | line
+    SMCMI_MAILBOX=$mb timeout 300 python bench.py --full --gpus 1 --steps 5 --warmup 1 --no-cpu --no-history --nparts $N 2>/dev/null | grep '^{' | tee $OUT/bench_n${N}_mb$mb.json | line
   done
-  (cd /tmp && export TMPDIR=/tmp && SMCMI_MAILBOX=2 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/kt_$N -o kt -- python $ROOT/bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu --no-history --nparts $N > /dev/null 2>&1)
+  (cd /tmp && export TMPDIR=/tmp && SMCMI_MAILBOX=2 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/kt_$N -o kt -- python $ROOT/bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu --no-history --nparts $N > /dev/null 2>&1)
   python profiles/summarize_rocpd.py $(find $OUT/kt_$N -name "*.db" | head -1) > $OUT/kernel_stats_n$N.txt
   python profiles/gaps_rocpd.py $(find $OUT/kt_$N -name "*.db" | head -1) 200 > $OUT/kernel_gaps_n$N.txt
   rm -rf $OUT/kt_$N
