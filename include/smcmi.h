@@ -166,8 +166,35 @@ int smcmi_eval_cloud_callback(smcmi_handle *h, int32_t which, int32_t column);
 int smcmi_callback_stats(smcmi_handle *h, int64_t *calls, int64_t *evaluations);   /* of the last smcmi_run */
 /* where the last run with a host callback spent its wall time on the calling thread, in ms (the first n <= 8 of: waiting for the propose
    kernel and the first chunk; waiting for later chunks; packing chunks that hold out-of-bounds proposals; inside the callback; NaN -> -Inf /
-   scatter; enqueueing copies and kernels; the stage's device part up to the proposal incl. its sync; reserved) */
+   scatter; enqueueing copies and kernels; the stage's device part up to the proposal incl. its sync; device callbacks only: waiting for the
+   propose kernel and the count of in-bounds proposals) */
 int smcmi_callback_phases(smcmi_handle *h, double *ms_out, int32_t n);
+
+/* ---- user likelihood on the DEVICE: the same closure for callers who can evaluate it on the GPU (a torch function, a HIP kernel of
+   their own).  The propose / accept split stays, but no proposal and no log-likelihood crosses PCIe: bounds gate, packing, NaN -> -Inf and
+   the redraw loop of the initial draw are HIP kernels on the handle's stream (csrc/devcallback.hpp).
+   theta: DEVICE pointer, m x d column-major with leading dimension ld (proposal k, parameter j at theta[k + ld * j]); only proposals
+   that passed the bounds check, in particle order (all of them: theta is the engine's own proposal buffer, ld = n_local, the same
+   pointer at every call; otherwise a packed copy, ld = m).  out: DEVICE pointer, m doubles.  stream: the hipStream_t of the handle; the
+   engine's writes to theta are ahead of the call on it and its reads of out are enqueued behind the call on it.  The function enqueues
+   its work on that stream, or makes that stream wait for its own work before it returns.  It need not synchronise; the engine never
+   reads out on the host.  Called on the thread that called smcmi_run / smcmi_run_group / smcmi_init_from_prior /
+   smcmi_initialize_likelihoods / smcmi_eval_cloud_callback, ONCE per MH step x block and vintage (no chunks); not called when no
+   proposal passed.  -Inf allowed; NaN is taken as -Inf by the engine.  Non-zero return: SMCMI_ERR_CALLBACK.
+   lik = NULL or lik->fn = NULL unregisters.  Registering replaces a host callback or a device family at `which`, and the other way
+   round.  A host callback on one vintage next to a device callback on the other: SMCMI_ERR_STATE from the run.  The only thing the host
+   reads per invocation is the count m (8 bytes, one stream synchronisation).  smcmi_run and smcmi_run_group (handles of one process)
+   serve device callbacks; smcmi_run_sharded (one process per rank) refuses them with SMCMI_ERR_UNSUPPORTED.
+   smcmi_callback_stats: calls = invocations, evaluations = the sum of m.  smcmi_callback_phases: the PCIe phases (waiting for chunks)
+   and the host-side pack / scatter are 0; `inside the callback` is the time the user's function took on the calling thread (enqueueing,
+   for an asynchronous one), `enqueueing` the engine's own launches, the stage's device part as before, and the last value - reserved
+   and 0 for host callbacks - the wait for the propose kernel and the count of in-bounds proposals. */
+typedef int (*smcmi_lik_device_fn)(const double *theta, int64_t m, int64_t ld, int64_t d, double *out, void *stream, void *user_data);
+typedef struct {
+    smcmi_lik_device_fn fn;
+    void *user_data;
+} smcmi_device_likelihood;
+int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const smcmi_device_likelihood *lik);
 
 /* ---- cloud transfer (cloud.particles; get_vals/get_loglh/... read columns of the download) ---- */
 int smcmi_upload_cloud(smcmi_handle *h, const double *particles);       /* n_local x R, column-major */

@@ -18,6 +18,7 @@ enum { CBP_FIRST = 0,      // propose kernel + the first chunk's way across PCIe
        CBP_SCATTER = 4,    // NaN -> -Inf pass / scatter of the packed results
        CBP_ENQUEUE = 5,    // enqueueing copies and kernels
        CBP_STAGE = 6,      // the stage's device part up to the proposal set-up, incl. the per-stage sync (run_callback)
+       CBP_COUNT = 7,      // device callbacks (devcallback.hpp): waiting for the propose kernel and the count of in-bounds proposals
        CBP_N = 8 };
 
 struct CallbackBuffers {
@@ -79,6 +80,10 @@ static int callback_chunks(long long n) {
     return (int)std::max<long long>(1, std::min<long long>(8, n / 12288));
 }
 static inline double cb_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static int ensure_split_buffers(smcmi_handle *h);
+#include "devcallback.hpp"
+// the phase clocks of the handle's kind of closure
+static inline double *cb_phase_ms(smcmi_handle *h) { return h->dcb[0] ? h->dcbuf->phase_ms : h->cbuf->phase_ms; }
 
 // Evaluate callback `which` on the m_rows x d column-major block `theta` (leading dimension m_rows) for the rows whose `gate` is finite
 // (gate = the proposals' log-priors: -Inf = the bounds check failed, the reference never calls the likelihood there, mutation.jl:93);
@@ -160,6 +165,7 @@ static int host_propose_enqueue(smcmi_handle *h, int step, int blk) {
     return 0;
 }
 static int host_mutation(smcmi_handle *h, const smcmi_run_config *rc, bool tempered, bool first_enqueued = false) {
+    if (h->dcb[0]) return device_mutation(h, rc, tempered);         // the likelihood is a device function: nothing crosses PCIe (devcallback.hpp)
     CallbackBuffers *b = h->cbuf;
     const long long n = h->n;
     const int d = h->d;
@@ -203,6 +209,7 @@ static int host_mutation(smcmi_handle *h, const smcmi_run_config *rc, bool tempe
 // loglh (and old_loglh) columns of the handle's cloud from the callbacks: initial clouds whose parameter columns were uploaded
 // without likelihood values (`smcmi_eval_cloud_callback`), and initialize_likelihoods! (src/initialization.jl:153-186)
 static int callback_fill_loglh(smcmi_handle *h, int which, int column) {
+    if (h->dcb[which]) return device_fill_loglh(h, which, column);
     if (int e = ensure_callback_buffers(h)) return e;
     CallbackBuffers *b = h->cbuf;
     const long long n = h->n;
@@ -220,6 +227,7 @@ static int callback_fill_loglh(smcmi_handle *h, int which, int column) {
 // (attempt a of particle i = the draws k_init_prior makes on its a-th outer attempt), the callback scores them, particles without
 // a finite log-likelihood are redrawn (one_draw's loop, :23-63) - the cloud a device family with the same values would start from.
 static int callback_init_from_prior(smcmi_handle *h) {
+    if (h->dcb[0]) return device_init_from_prior(h);
     // (the Gamma-family draws keep their acceptance uniforms in tag k | 64: beyond 64 parameters that collides with parameter k's normal)
     if (h->d > 64) return set_err(SMCMI_ERR_UNSUPPORTED, "device prior draws serve n_para <= 64");
     if (int e = ensure_callback_buffers(h)) return e;
@@ -264,9 +272,10 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     if (rc->resampling_method != SMCMI_RESAMPLE_SYSTEMATIC && rc->resampling_method != SMCMI_RESAMPLE_MULTINOMIAL)
         return set_err(SMCMI_ERR_ARG, "Invalid resampler in SMC. Options are systematic or multinomial");
     const bool adaptive = !rc->use_fixed_schedule;
-    const bool tempered = h->cb[1] != nullptr;
+    const bool tempered = closure_lik(h, 1);
+    const bool on_device = h->dcb[0] != nullptr;          // the likelihood is a device function (devcallback.hpp): no staging buffers, no copy streams
     if (!adaptive && rc->n_phi > h->cfg.max_stages) return set_err(SMCMI_ERR_CAPACITY, "max_stages < n_phi");
-    if (int e = ensure_callback_buffers(h)) return e;
+    if (int e = on_device ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e;
     if (pull_state(h)) return SMCMI_ERR_HIP;
     std::vector<double> sched(rc->n_phi);
     for (int k = 0; k < rc->n_phi; ++k) sched[k] = pow((double)k / (double)(rc->n_phi - 1), rc->lambda);
@@ -321,7 +330,8 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     const auto t0 = std::chrono::steady_clock::now();
     const int max_iter = (adaptive ? h->cfg.max_stages : rc->n_phi - 1) - base;
     h->cb_calls = 0; h->cb_evals = 0;
-    for (double &p : h->cbuf->phase_ms) p = 0.0;
+    double *phase_ms = cb_phase_ms(h);
+    for (int k = 0; k < CBP_N; ++k) phase_ms[k] = 0.0;
     res->solver_stalls = 0; res->select_stalls = 0; res->spec_stalls = 0;
     int launched = 0, done = 0, had = first_passes;
     DevState head;
@@ -335,6 +345,12 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
         bool first_enqueued = false;
         for (;;) {
             HIP_TRY(hipMemcpyAsync((char *)&head + head_off, (const char *)h->d_st + head_off, head_len, hipMemcpyDeviceToHost, h->stream));
+            if (on_device) {
+                // (a device callback proposes once the verdict is known: its first wait is the count of in-bounds proposals anyway)
+                HIP_TRY(hipStreamSynchronize(h->stream));
+                done = head.done;
+                if (done != 2) break;
+            } else {
             HIP_TRY(hipEventRecord(h->cbuf->ev_head, h->stream));
             // the first proposal goes out before the verdict is read (a stage that stalled or ended leaves it a no-op)
             if (ensure_split_buffers(h)) return SMCMI_ERR_HIP;
@@ -345,6 +361,7 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
             if (done != 2) break;
             first_enqueued = false;
             HIP_TRY(hipStreamSynchronize(h->cbuf->s_down));          // (the dropped proposal's copies: the pinned buffers are reused below)
+            }
             if (had > 1200) return set_err(SMCMI_ERR_BRACKET, "adaptive tempering solver: the search for phi_n does not terminate (the ESS objective is not a number?)");
             // the solver ran out of passes: continue the same search with more (smcmi_run)
             const int zero = 0;
@@ -353,13 +370,13 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
             had += 8;
             res->solver_stalls += 1;
         }
-        h->cbuf->phase_ms[CBP_STAGE] += cb_now_ms() - ts0;
+        phase_ms[CBP_STAGE] += cb_now_ms() - ts0;
         if (done) break;                                 // ϕ = 1 was reached by the previous stage (its begin raised the flag), a pause, or an error
         if (int e = host_mutation(h, rc, tempered, first_enqueued)) return e;
         ++launched;
     }
     k_stage_begin<<<1, BT, 0, h->stream>>>(h->d_st, h->d_sched, h->d_acc_part, acc_nb, h->rec);
-    HIP_TRY(hipStreamSynchronize(h->cbuf->s_down));                  // (a proposal enqueued for a stage that turned out to be the end of the run)
+    if (!on_device) HIP_TRY(hipStreamSynchronize(h->cbuf->s_down));  // (a proposal enqueued for a stage that turned out to be the end of the run)
     if (pull_state(h)) return SMCMI_ERR_HIP;
     const auto t1 = std::chrono::steady_clock::now();
     res->kernel_ms_mutate = 0.0; res->n_mutate_launches = 0;

@@ -22,6 +22,7 @@
 
 using namespace smcmi;
 struct CallbackBuffers;            // pinned staging buffers of the host-likelihood path (callback.hpp)
+struct DevCallbackBuffers;         // count / pack / scatter buffers of the device-callback path (devcallback.hpp)
 
 struct Eng2 {
     Geo2 g{};
@@ -133,4 +134,10 @@ struct smcmi_handle {
     CallbackBuffers *cbuf = nullptr;
     long long cb_calls = 0, cb_evals = 0;
     bool cb_energy = false;        // the run's accept launches leave energy power sums / maxima (adaptive single-handle closure runs: predictor rings, shifted weights)
+    // user likelihoods that are device functions (devcallback.hpp): they take the closure run's paths, without the PCIe crossings
+    smcmi_lik_device_fn dcb[2] = {nullptr, nullptr};
+    void *dcb_ud[2] = {nullptr, nullptr};
+    DevCallbackBuffers *dcbuf = nullptr;
 };
+// is likelihood `which` of the handle a user closure - a host callback or a device callback?  (which = 0: "this is a closure run")
+static inline bool closure_lik(const smcmi_handle *h, int which = 0) { return h->cb[which] != nullptr || h->dcb[which] != nullptr; }

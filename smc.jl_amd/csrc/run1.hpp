@@ -74,9 +74,12 @@ static void enqueue_stage(smcmi_handle *h, bool adaptive, int solver_passes, int
 // would call a device family that does not exist - refuse instead of sampling the wrong posterior
 static int check_lik_pair(const smcmi_handle *h) {
     const int f1 = h->h_model.lik[1].family;
-    const bool old_dev = f1 != SMCMI_LIK_NONE && f1 != SMCMI_LIK_HOST_CALLBACK, old_cb = h->cb[1] != nullptr;
-    if ((h->cb[0] && old_dev) || (!h->cb[0] && old_cb))
+    const bool old_dev = f1 != SMCMI_LIK_NONE && f1 != SMCMI_LIK_HOST_CALLBACK, old_cb = closure_lik(h, 1);
+    if ((closure_lik(h) && old_dev) || (!closure_lik(h) && old_cb))
         return set_err(SMCMI_ERR_UNSUPPORTED, "the new and the old likelihood must both be device families or both host callbacks");
+    // (a host callback next to a device callback: one mutation would need both paths)
+    if ((h->cb[0] && h->dcb[1]) || (h->dcb[0] && h->cb[1]))
+        return set_err(SMCMI_ERR_STATE, "the new and the old likelihood must both be host callbacks or both device callbacks");
     return 0;
 }
 struct ShardGroup;
@@ -91,7 +94,7 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
     res->n_segments = 0; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
     res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
     if (int e = check_lik_pair(h)) return e;
-    if (h->cb[0]) return run_callback(h, rc, res);                    // user likelihood on the host (callback.hpp)
+    if (closure_lik(h)) return run_callback(h, rc, res);              // user likelihood: a host callback or a device callback (callback.hpp)
     if (eng2_eligible(h, 1, true, rc)) return run2_single(h, rc, res);          // n_para <= 10: the two-launch stage (stage2.hpp)
     const int nf = h->h_model.n_free;
     if (rc->n_blocks < 1 || rc->n_blocks > nf || ((nf + rc->n_blocks - 1) / rc->n_blocks) * (rc->n_blocks - 1) >= nf)

@@ -346,9 +346,10 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     // kernel -> closure on the calling thread -> accept kernel), everything else - solver passes, correction, selection, moments,
     // proposal set-up, the collectives - is this driver's.  The callback mutation leaves neither energy sums nor energy maxima, so
     // such runs walk the schedule without a predictor, unshifted, one stage per host sync (the closure needs the host anyway).
-    const bool host_mut = h0->cb[0] != nullptr, tempered_cb = h0->cb[1] != nullptr;
+    // (a device callback - smcmi_set_likelihood_device - takes the same route: host_mutation branches on the kind)
+    const bool host_mut = closure_lik(h0), tempered_cb = closure_lik(h0, 1), dev_cb = h0->dcb[0] != nullptr;
     for (auto *h : g.hs)
-        if ((h->cb[0] != nullptr) != host_mut || (h->cb[1] != nullptr) != tempered_cb) return set_err(SMCMI_ERR_STATE, "every shard needs the same likelihood callbacks");
+        if (closure_lik(h) != host_mut || closure_lik(h, 1) != tempered_cb || (h->dcb[0] != nullptr) != dev_cb) return set_err(SMCMI_ERR_STATE, "every shard needs the same likelihood callbacks");
     const bool predict = adaptive && !no_pred && !host_mut;
     static const int sel_mode = getenv("SMCMI_NO_SELECT_PREDICT") ? atoi(getenv("SMCMI_NO_SELECT_PREDICT")) : 0;   // development only
     const bool predict_select = adaptive && can_fuse_post(h0) && sel_mode != 1 && !host_mut;
@@ -358,7 +359,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
         HIP_TRY(hipSetDevice(h->cfg.device));
         if (!adaptive && rc->n_phi > h->cfg.max_stages) return set_err(SMCMI_ERR_CAPACITY, "max_stages < n_phi");
         if (ensure_shard_buffers(h) || pull_state(h) || upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
-        if (host_mut) { if (int e = ensure_callback_buffers(h)) return e; h->rng_ahead = false; h->cb_energy = false; h->cb_calls = 0; h->cb_evals = 0; }
+        if (host_mut) { if (int e = dev_cb ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e; h->rng_ahead = false; h->cb_energy = false; h->cb_calls = 0; h->cb_evals = 0; }
         else if (int e = ensure_zbuf(h, rc->n_mh_steps, rc->n_blocks)) return e;
         DevState &s = h->h_st;
         RunParams rp{};
@@ -752,9 +753,10 @@ extern "C" int smcmi_run_sharded(smcmi_handle *h, const smcmi_run_config *rc, sm
     res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
     if (!h->nccl && !h->has_hostc) return set_err(SMCMI_ERR_STATE, "smcmi_comm_init / smcmi_comm_init_host has not been called on this handle");
     if (int e = check_lik_pair(h)) return e;
+    if (h->dcb[0]) return set_err(SMCMI_ERR_UNSUPPORTED, "device likelihood callbacks serve one process (smcmi_run, smcmi_run_group); a multi-process run needs host callbacks or a device family");
     ShardGroup g;
     g.hs = {h}; g.world = h->world; g.rccl = true; g.hostc = h->has_hostc;
-    if (!h->cb[0] && eng2_eligible(h, g.world, false, rc)) return run2_guarded(g, rc, res);      // n_para <= 10: the two-launch stage (stage2.hpp / run2.hpp)
+    if (!closure_lik(h) && eng2_eligible(h, g.world, false, rc)) return run2_guarded(g, rc, res);      // n_para <= 10: the two-launch stage (stage2.hpp / run2.hpp)
     return run_sharded_impl(g, rc, res);                                             // n_para > 10, and every run with a host likelihood
 }
 
@@ -774,6 +776,6 @@ extern "C" int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_con
     }
     if (expect != hs[0]->cfg.n_parts) return set_err(SMCMI_ERR_ARG, "group handles do not cover n_parts");
     g.world = n; g.rccl = false;
-    if (!hs[0]->cb[0] && eng2_eligible(hs[0], g.world, n == 1, rc)) return run2_guarded(g, rc, res);
+    if (!closure_lik(hs[0]) && eng2_eligible(hs[0], g.world, n == 1, rc)) return run2_guarded(g, rc, res);
     return run_sharded_impl(g, rc, res);
 }

@@ -10,6 +10,7 @@
 
 static void free_eng2(Eng2 *e);
 static void free_callback_buffers(CallbackBuffers *b);
+static void free_dev_callback_buffers(DevCallbackBuffers *b);
 
 static thread_local std::string g_err;
 extern "C" const char *smcmi_last_error(void) { return g_err.c_str(); }
@@ -214,6 +215,7 @@ extern "C" int smcmi_destroy(smcmi_handle *h) {
     if (h->d_mbox) { hipFree(h->d_mbox); h->d_mbox = nullptr; }
     if (h->d_peers) { hipFree(h->d_peers); h->d_peers = nullptr; }
     if (h->cbuf) { free_callback_buffers(h->cbuf); h->cbuf = nullptr; }
+    if (h->dcbuf) { free_dev_callback_buffers(h->dcbuf); h->dcbuf = nullptr; }
     if (h->h_note) { hipHostFree((void *)h->h_note); h->h_note = nullptr; h->d_note = nullptr; }
     void *ptrs[] = {h->cl.buf[0], h->cl.buf[1], h->d_st, h->d_model, h->d_data[0], h->d_data[1], h->d_aux[0], h->d_aux[1],
                     h->rec.phi, h->rec.ess, h->rec.c, h->rec.accept, h->rec.resampled, h->d_sched, h->d_part_ess[0], h->d_part_ess[1],
@@ -280,6 +282,7 @@ extern "C" int smcmi_set_likelihood(smcmi_handle *h, int32_t which, int32_t fami
     memset(&l, 0, sizeof(LikDev));
     l.family = family;
     h->cb[which] = nullptr; h->cb_ud[which] = nullptr;            // a device family (or none) replaces a registered host callback
+    h->dcb[which] = nullptr; h->dcb_ud[which] = nullptr;          // ... or device callback
     if (family == SMCMI_LIK_NONE || family == SMCMI_LIK_HOST_CALLBACK) {
         h->lik_host_data[which].clear(); h->lik_host_aux[which].clear();
         update_lik_prefix(h);
@@ -377,7 +380,7 @@ static int need_model(smcmi_handle *h, int lik) {
     if (!h->have_params) return set_err(SMCMI_ERR_STATE, "smcmi_set_parameters has not been called");
     // lik: 1 = a device family is required (kernels evaluate it), 2 = a device family or a registered host callback
     const bool dev_ok = h->have_lik && h->h_model.lik[0].family >= 0 && h->h_model.lik[0].family != SMCMI_LIK_HOST_CALLBACK;
-    if (lik && !(dev_ok || (lik_level(lik) == 2 && h->cb[0] != nullptr)))
+    if (lik && !(dev_ok || (lik_level(lik) == 2 && closure_lik(h))))
         return set_err(SMCMI_ERR_STATE, "no likelihood set (smcmi_set_likelihood; smcmi_set_likelihood_callback for smcmi_run / smcmi_initialize_likelihoods)");
     hipError_t e = hipSetDevice(h->cfg.device);
     if (e != hipSuccess) return set_err(SMCMI_ERR_HIP, "hipSetDevice failed");
@@ -387,7 +390,7 @@ static int need_model(smcmi_handle *h, int lik) {
 static int callback_init_from_prior(smcmi_handle *h);
 extern "C" int smcmi_init_from_prior(smcmi_handle *h) {
     if (int rc = need_model(h, 2)) return rc;
-    if (h->cb[0]) return callback_init_from_prior(h);                 // user likelihood: device draws, host scores
+    if (closure_lik(h)) return callback_init_from_prior(h);           // user likelihood: device draws, the callback scores
     if (h->d > 64) return set_err(SMCMI_ERR_UNSUPPORTED, "device prior sampling: the RNG tags carry the parameter index in 6 bits");
     HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
     k_init_prior<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_model, h->cfg.seed, h->cfg.gid0, h->d_flag);
@@ -403,14 +406,14 @@ static bool use_ls4_mutate(const smcmi_handle *h);
 static bool use_wave_kalman(const smcmi_handle *h);
 extern "C" int smcmi_initialize_likelihoods(smcmi_handle *h) {
     if (int rc = need_model(h, 2)) return rc;
-    if (use_ls4_mutate(h) && !h->cb[0])
+    if (use_ls4_mutate(h) && !closure_lik(h))
         k_initialize_likelihoods<4><<<(unsigned)((h->n + 63) / 64), 256, 64 * KALMAN4_SLOT_BYTES, h->stream>>>(h->cl, h->d_model);
-    else if (use_wave_kalman(h) && !h->cb[0])
+    else if (use_wave_kalman(h) && !closure_lik(h))
         k_initialize_likelihoods<1><<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_model);
     else
         k_initialize_likelihoods<0><<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_model);
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->cb[0]) return callback_fill_loglh(h, 0, h->d);            // host likelihood: the kernel retired loglh and evaluated the prior
+    if (closure_lik(h)) return callback_fill_loglh(h, 0, h->d);      // user likelihood: the kernel retired loglh and evaluated the prior
     return 0;
 }
 
@@ -419,6 +422,7 @@ extern "C" int smcmi_set_likelihood_callback(smcmi_handle *h, int32_t which, smc
     if (!h || which < 0 || which > 1) return set_err(SMCMI_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->cfg.device));
     h->cb[which] = fn; h->cb_ud[which] = user_data;
+    h->dcb[which] = nullptr; h->dcb_ud[which] = nullptr;          // a host callback (or none) replaces a registered device callback
     LikDev &l = h->h_model.lik[which];
     if (h->d_data[which]) { hipFree(h->d_data[which]); h->d_data[which] = nullptr; }
     if (h->d_aux[which]) { hipFree(h->d_aux[which]); h->d_aux[which] = nullptr; }
@@ -427,9 +431,26 @@ extern "C" int smcmi_set_likelihood_callback(smcmi_handle *h, int32_t which, smc
     if (which == 0) h->have_lik = fn != nullptr;
     return push_model(h);
 }
+// ---- the same closure as a DEVICE function: device pointers and the handle's stream in, nothing crosses PCIe (devcallback.hpp)
+extern "C" int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const smcmi_device_likelihood *lik) {
+    if (!h || which < 0 || which > 1) return set_err(SMCMI_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    smcmi_lik_device_fn fn = lik ? lik->fn : nullptr;
+    h->dcb[which] = fn; h->dcb_ud[which] = fn ? lik->user_data : nullptr;
+    h->cb[which] = nullptr; h->cb_ud[which] = nullptr;            // replaces a registered host callback or device family
+    LikDev &l = h->h_model.lik[which];
+    if (h->d_data[which]) { hipFree(h->d_data[which]); h->d_data[which] = nullptr; }
+    if (h->d_aux[which]) { hipFree(h->d_aux[which]); h->d_aux[which] = nullptr; }
+    memset(&l, 0, sizeof(LikDev));
+    l.family = fn ? SMCMI_LIK_HOST_CALLBACK : SMCMI_LIK_NONE;      // (to the kernels both kinds of closure are "not evaluated here")
+    h->lik_host_data[which].clear(); h->lik_host_aux[which].clear();
+    update_lik_prefix(h);
+    if (which == 0) h->have_lik = fn != nullptr;
+    return push_model(h);
+}
 extern "C" int smcmi_eval_cloud_callback(smcmi_handle *h, int32_t which, int32_t column) {
     if (int rc = need_model(h, false)) return rc;
-    if (which < 0 || which > 1 || !h->cb[which]) return set_err(SMCMI_ERR_STATE, "no likelihood callback registered");
+    if (which < 0 || which > 1 || !closure_lik(h, which)) return set_err(SMCMI_ERR_STATE, "no likelihood callback registered");
     if (column != h->d && column != h->d + 2) return set_err(SMCMI_ERR_ARG, "column must be the loglh (n_para) or old_loglh (n_para + 2) column");
     return callback_fill_loglh(h, which, column);
 }
@@ -1118,7 +1139,8 @@ extern "C" int smcmi_shard_mutate_partial(smcmi_handle *h, const double *mu_free
 #include "callback.hpp"
 extern "C" int smcmi_callback_phases(smcmi_handle *h, double *ms_out, int32_t n) {
     if (!h || !ms_out || n < 1) return set_err(SMCMI_ERR_ARG, "bad argument");
-    for (int k = 0; k < n; ++k) ms_out[k] = (h->cbuf && k < CBP_N) ? h->cbuf->phase_ms[k] : 0.0;
+    const double *ms = h->dcb[0] ? (h->dcbuf ? h->dcbuf->phase_ms : nullptr) : (h->cbuf ? h->cbuf->phase_ms : nullptr);
+    for (int k = 0; k < n; ++k) ms_out[k] = (ms && k < CBP_N) ? ms[k] : 0.0;
     return 0;
 }
 #include "sharded.hpp"

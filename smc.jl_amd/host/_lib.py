@@ -62,6 +62,16 @@ class StageStats(C.Structure):
 # int (*smcmi_lik_callback)(const double *theta, int64_t m, int64_t d, double *out, void *user_data)
 LIK_CALLBACK = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_void_p)
 
+# int (*smcmi_lik_device_fn)(const double *theta, int64_t m, int64_t ld, int64_t d, double *out, void *stream, void *user_data):
+# theta, out and stream are DEVICE pointers / a hipStream_t - plain addresses here
+LIK_DEVICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+class DeviceLik(C.Structure):
+    """smcmi_device_likelihood"""
+    _fields_ = [("fn", LIK_DEVICE_FN), ("user_data", C.c_void_p)]
+
+
 # smcmi_host_comm: the collectives of a sharded run as host functions (include/smcmi.h)
 HC_ALLGATHER = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_void_p)
 HC_ALLTOALLV = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),
@@ -83,6 +93,7 @@ SYMBOLS = [
     ("smcmi_set_parameters", C.c_int, [_H, ip, dp, dp, ip, dp, dp]),
     ("smcmi_set_likelihood", C.c_int, [_H, C.c_int32, C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int64]),
     ("smcmi_set_likelihood_callback", C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("smcmi_set_likelihood_device", C.c_int, [_H, C.c_int32, C.c_void_p]),      # const smcmi_device_likelihood * (C.byref(DeviceLik) or None)
     ("smcmi_eval_cloud_callback", C.c_int, [_H, C.c_int32, C.c_int32]),
     ("smcmi_callback_stats", C.c_int, [_H, lp, lp]),
     ("smcmi_callback_phases", C.c_int, [_H, dp, C.c_int32]),

@@ -183,6 +183,37 @@ class CapmLiteral(DeviceLikelihood):
         return ("capm_literal", [], np.asarray(data, dtype=np.float64), self.market)
 
 
+class TorchLikelihood:
+    """A user likelihood that runs on the GPU: fn(theta, data) -> m log-likelihoods, with theta an (m, d) torch.float64 CUDA tensor
+    (the proposals that passed the bounds check, in particle order; a zero-copy view of the engine's buffer) and `data` a CUDA tensor
+    uploaded once.  smc(TorchLikelihood(fn), parameters, data, ...) routes it through Engine.set_likelihood_device: the closure
+    path of the reference's smc(loglikelihood::Function, ...), without the proposals and the scores crossing PCIe."""
+
+    def __init__(self, fn):
+        if not callable(fn):
+            raise TypeError("TorchLikelihood wraps a callable fn(theta, data)")
+        self.fn = fn
+
+    def bind(self, data, device):
+        """fn with `data` resident on `device`: what Engine.set_likelihood_device takes"""
+        import torch
+
+        dat = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float64), device="cuda:%d" % device)
+        fn = self.fn
+        return lambda th: fn(th, dat)
+
+
+def _lik_kind(lik):
+    """'family' (device family), 'host' (Python callable) or 'device' (TorchLikelihood) of a likelihood spec tuple"""
+    return {"host_callback": "host", "device_callback": "device"}.get(lik[0], "family")
+
+
+def _lik_spec(lik, data):
+    if isinstance(lik, DeviceLikelihood):
+        return lik.spec(data)
+    return ("device_callback" if isinstance(lik, TorchLikelihood) else "host_callback", [], None, None)
+
+
 # ----------------------------------------------------------------------------------------------- Cloud
 class Cloud:
     """src/particle.jl:31-53.  particles: (n_parts, n_params + 5) float64, Fortran order."""
@@ -307,14 +338,17 @@ def smc(loglikelihood, parameters, data, *, verbose="low", n_parts=5000, n_block
         from .cloudio import load_cloud
         old_cloud = load_cloud(loadpath)[0]                       # cloud_isempty(old_cloud) ? load(loadpath, "cloud") : old_cloud
     data = np.asarray(data, dtype=np.float64)
-    device_lik = isinstance(loglikelihood, DeviceLikelihood)
-    lik = loglikelihood.spec(data) if device_lik else ("host_callback", [], None, None)
+    lik = _lik_spec(loglikelihood, data)
     old_lik = None
     tempered = old_data is not None and np.size(old_data) > 0
     if tempered:
         ol = old_loglikelihood if old_loglikelihood is not None else loglikelihood
-        old_lik = ol.spec(np.asarray(old_data, dtype=np.float64)) if isinstance(ol, DeviceLikelihood) else ("host_callback", [], None, None)
-    if tempered and (lik[0] == "host_callback") != (old_lik[0] == "host_callback"):
+        old_lik = _lik_spec(ol, np.asarray(old_data, dtype=np.float64))
+    if tempered and {_lik_kind(lik), _lik_kind(old_lik)} == {"host", "device"}:
+        # (one mutation would need the host path and the device path; smcmi_run refuses the pair as well)
+        raise NotImplementedError("tempered update: loglikelihood and old_loglikelihood must both be Python callables or both "
+                                  "TorchLikelihood objects")
+    if tempered and (_lik_kind(lik) == "family") != (_lik_kind(old_lik) == "family"):
         # one likelihood on the device and the other a host closure: the callback path scores both on the host, the device path both on
         # the device - a mixed pair would silently lose the old likelihood (csrc/callback.hpp); smcmi_run rejects it as well
         raise NotImplementedError("tempered update: loglikelihood and old_loglikelihood must both be DeviceLikelihood objects or both "
@@ -331,16 +365,11 @@ def smc(loglikelihood, parameters, data, *, verbose="low", n_parts=5000, n_block
         """priors + the (new, old) likelihood pair on engine e: device families through smcmi_set_likelihood, Python callables
         through smcmi_set_likelihood_callback (the reference's per-particle closure, batched by a trampoline)."""
         e.set_parameters(spec["priors"], spec["bounds"], spec["fixed"])
-        if new_lik[0] == "host_callback":
-            e.set_likelihood_callback(_batch(new_fn, data), which=0)
-        else:
-            e.set_likelihood(*new_lik, which=0)
+        _set_lik_on(e, new_lik, new_fn, data, 0, device)
         if old_lik_ is None:
             e.set_likelihood("none", which=1)
-        elif old_lik_[0] == "host_callback":
-            e.set_likelihood_callback(_batch(old_fn, old_dat), which=1)
         else:
-            e.set_likelihood(*old_lik_, which=1)
+            _set_lik_on(e, old_lik_, old_fn, old_dat, 1, device)
 
     old_fn = (old_loglikelihood if old_loglikelihood is not None else loglikelihood) if tempered else None
     old_dat = np.asarray(old_data, dtype=np.float64) if tempered else None
@@ -359,10 +388,7 @@ def smc(loglikelihood, parameters, data, *, verbose="low", n_parts=5000, n_block
             # prior draws scored by the OLD likelihood on the old data (smc_main.jl:288-291)
             pri = Engine(n_pr, d, seed=seed, device=device, max_stages=2, store_history=False)
             pri.set_parameters(spec["priors"], spec["bounds"], spec["fixed"])
-            if old_lik[0] == "host_callback":
-                pri.set_likelihood_callback(_batch(old_fn, old_dat), which=0)
-            else:
-                pri.set_likelihood(*old_lik, which=0)
+            _set_lik_on(pri, old_lik, old_fn, old_dat, 0, device)
             pri.set_likelihood("none", which=1)
             pri.init_from_prior()
             return pri
@@ -503,6 +529,17 @@ def _safe_call(f, th, data):
     except (ArithmeticError, ValueError, np.linalg.LinAlgError):
         return -math.inf
     return -math.inf if math.isnan(v) else v
+
+
+def _set_lik_on(e, lik, fn, data, which, device):
+    """likelihood `which` of engine e from its spec tuple: a device family, a Python callable (host callback) or a TorchLikelihood
+    (device callback)"""
+    if lik[0] == "host_callback":
+        e.set_likelihood_callback(_batch(fn, data), which=which)
+    elif lik[0] == "device_callback":
+        e.set_likelihood_device(fn.bind(data, device), which=which)
+    else:
+        e.set_likelihood(*lik, which=which)
 
 
 def _batch(fn, data):

@@ -92,6 +92,47 @@ class Engine:
         self._cb[which] = cb
         check(self._L.smcmi_set_likelihood_callback(self._h, which, C.cast(cb, C.c_void_p), None))
 
+    def set_likelihood_device(self, fn, which=0):
+        """Register a likelihood that runs on the GPU (smcmi_set_likelihood_device): fn(theta) with theta a zero-copy torch.float64
+        CUDA tensor of shape (m, d), strides (1, ld) - the proposals that passed the bounds check, in particle order - returning a
+        tensor of m log-likelihoods on the same device (-inf allowed, NaN is taken as -inf).  fn runs under the handle's stream
+        (torch.cuda.ExternalStream), so what it enqueues is ordered behind the proposal kernel and ahead of the accept kernel without
+        a synchronisation; no proposal and no log-likelihood crosses PCIe.  fn = None unregisters.  Exceptions inside fn, and a result
+        of the wrong shape or dtype, abort the run (SMCMI_ERR_CALLBACK) before anything of fn's batch is used and are re-raised by
+        run() / init_from_prior() / ..."""
+        if not hasattr(self, "_cb"):
+            self._cb, self._cb_exc = [None, None], None
+        if fn is None:
+            self._cb[which] = None
+            check(self._L.smcmi_set_likelihood_device(self._h, which, None))
+            return
+        import torch
+
+        def tramp(theta_p, m, ld, d, out_p, stream_p, _ud):
+            try:
+                m, ld, d = int(m), int(ld), int(d)
+                # theta[k + ld * j]: (d, ld) row-major -> the first m entries of every row, transposed: (m, d) with strides (1, ld)
+                th = self._dev_tensor(theta_p, (d, ld))[:, :m].T
+                out = self._dev_tensor(out_p, (m,))
+                with torch.cuda.stream(torch.cuda.ExternalStream(int(stream_p or 0), device=th.device)):
+                    val = fn(th)
+                    if not isinstance(val, torch.Tensor):
+                        raise TypeError("a device likelihood returns a torch tensor, got %s" % type(val).__name__)
+                    if val.device != th.device or val.dtype != torch.float64:
+                        raise TypeError("a device likelihood returns a float64 tensor on %s, got %s on %s" % (th.device, val.dtype, val.device))
+                    if val.numel() != m or val.dim() > 2 or (val.dim() == 2 and 1 not in val.shape):
+                        raise ValueError("a device likelihood returns %d log-likelihoods, got a tensor of shape %s" % (m, tuple(val.shape)))
+                    out.copy_(val.reshape(m))
+                return 0
+            except BaseException as ex:   # noqa: BLE001 - must not unwind through the C frames
+                self._cb_exc = ex
+                return 1
+
+        cb = _lib.LIK_DEVICE_FN(tramp)
+        st = _lib.DeviceLik(cb, None)
+        self._cb[which] = (cb, st)
+        check(self._L.smcmi_set_likelihood_device(self._h, which, C.byref(st)))
+
     def eval_cloud_callback(self, which=0, column=None):
         self._checked(self._L.smcmi_eval_cloud_callback(self._h, which, self.d if column is None else int(column)))
 
@@ -104,7 +145,7 @@ class Engine:
         """ms the last run with a host callback spent per phase on the calling thread (include/smcmi.h smcmi_callback_phases)"""
         out = (C.c_double * 8)()
         check(self._L.smcmi_callback_phases(self._h, out, 8))
-        names = ("first_chunk_wait", "later_chunk_wait", "pack", "callback", "scatter", "enqueue", "stage_device_part")
+        names = ("first_chunk_wait", "later_chunk_wait", "pack", "callback", "scatter", "enqueue", "stage_device_part", "count_wait")
         return {k: out[i] for i, k in enumerate(names)}
 
     def set_model(self, spec):
