@@ -296,6 +296,7 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
         if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
         if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");
         s.rp = rp; s.done = 0; s.err = 0; s.skip_fold = 1; s.do_resample = 0;
+        s.e_seen = __builtin_nan("");                           // (as run1.hpp: this path keeps no Begin2::e_seen)
     } else {
         const int cur = s.cur;
         memset(&s, 0, sizeof(DevState));

@@ -625,8 +625,11 @@ __device__ inline void solver_prologue(DevState *st, const double *sched, const 
 // (large-sample tempered updates) - the reference normalises before squaring (helpers.jl:173-181) and survives to |δ e| ~ 745,
 // unshifted sums of squares give up at ~354.  ESS, normalised weights and moments are ratios and do not see the common factor;
 // log(Σ W̃ / N) gets δ e_shift back (post_load) and the stored incremental weights their factor exp(δ e_shift).
-// Prior-weight corrections (pw != 0) use another exponent and stay unshifted, like the stand-alone calls (e_shift = 0).
-__device__ inline double stage_shift(const DevState *st) { return st->rp.pw == 0.0 ? st->e_shift : 0.0; }
+// Prior-weight corrections (pw != 0) use another exponent, δ g with the generalised energy g = loglh - log(exp(old - logp_old + log(1 - pw)) + pw)
+// (pw == 1: g = loglh): the maximum that is tracked is g's (energy_base below), so the same shift puts them into the same range.  The solver
+// passes of an adaptive schedule always use e (quirk Q4) and take the stage's shift as it is.  The stand-alone calls (smcmi_correct,
+// smcmi_ess_at, smcmi_solve_phi) take the cloud's maximum with one k_energy_max launch of their own.
+__device__ inline double stage_shift(const DevState *st) { return st->e_shift; }
 
 // max over the block of v (-inf for lanes without a value); smem: one double per wavefront; all threads must call
 __device__ inline double block_max(double v, double *smem, int nwaves) {
@@ -638,6 +641,10 @@ __device__ inline double block_max(double v, double *smem, int nwaves) {
     double m = smem[0];
     for (int w = 1; w < nwaves; ++w) m = fmax(m, smem[w]);
     return m;
+}
+// what the correction's exponent subtracts from loglh: old_loglh (pw == 0: the same value, nothing is computed), 0 (pw == 1) or the mixture's log
+__device__ inline double energy_base(double like_prev, double pw, double logp_old) {
+    return pw == 0.0 ? like_prev : (pw == 1.0 ? 0.0 : log(exp(like_prev - logp_old + log(1.0 - pw)) + pw));
 }
 __device__ inline double energy_or_ninf(double like, double like_prev, double w, bool live) {
     const double e = like - like_prev;
@@ -653,10 +660,11 @@ static __global__ void __launch_bounds__(TB) k_energy_max(CloudPtrs cl, const De
     __shared__ double smem[TB / 64];
     const int R = cl.R, src = buf >= 0 ? buf : st->cur;
     const double *loglh = col(cl, src, R - 5), *old = col(cl, src, R - 3), *w = col(cl, src, R - 1);
+    const double pw = st->rp.pw, logp_old = st->rp.logp_old;
     long long beg, end;
     block_chunk(cl.n, gridDim.x, blockIdx.x, beg, end);
     double m = -__builtin_inf();
-    for (long long i = beg + threadIdx.x; i < end; i += TB) m = fmax(m, energy_or_ninf(loglh[i], old[i], w[i], true));
+    for (long long i = beg + threadIdx.x; i < end; i += TB) m = fmax(m, energy_or_ninf(loglh[i], energy_base(old[i], pw, logp_old), w[i], true));
     m = block_max(m, smem, TB / 64);
     if (threadIdx.x == 0) emax_part[(long long)blockIdx.x * stride] = m;
 }
@@ -2353,7 +2361,7 @@ __global__ void __launch_bounds__(256, 1) k_mutate(CloudPtrs cl, const DevState 
     if (leaves_sums && ma.emax) {                    // largest energy of the mutated cloud (energy shift of the next stage)
         __shared__ double emx[4];
         const double wl = (counted && !st->do_resample) ? col(cl, src, d + 4)[i] : 1.0;
-        const double em = block_max(energy_or_ninf(like, like_prev, wl, counted), emx, nwv);
+        const double em = block_max(energy_or_ninf(like, energy_base(like_prev, st->rp.pw, st->rp.logp_old), wl, counted), emx, nwv);
         if (btid == 0) ma.emax[blockIdx.x] = em;
     }
     if (leaves_sums && ma.esum) {                    // energy power sums of the mutated cloud (ϕ predictor of the next stage)
@@ -2878,7 +2886,7 @@ SMCMI_FP_CONTRACT
     __syncthreads();
     // largest energy of the mutated cloud (energy shift of the next stage): wave maxima ride along with the acceptance sums
     __shared__ double emx[4];
-    double em = energy_or_ninf(like, like_prev, (ma.esum && !es_uniform) ? w_part : 1.0, live);
+    double em = energy_or_ninf(like, energy_base(like_prev, st->rp.pw, st->rp.logp_old), (ma.esum && !es_uniform) ? w_part : 1.0, live);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) em = fmax(em, __shfl_xor(em, off, 64));
     if ((tid & 63) == 0) { red[tid >> 6] = a1[0]; emx[tid >> 6] = em; }

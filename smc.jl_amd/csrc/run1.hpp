@@ -128,6 +128,7 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
         if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
         if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");
         s.rp = rp; s.done = 0; s.err = 0; s.skip_fold = 1; s.do_resample = 0;
+        s.e_seen = __builtin_nan("");                           // (engine 1 keeps no Begin2::e_seen: a later continuation on engines 2 / 3 takes the cloud's own maximum)
     } else {
         memset(&s, 0, sizeof(DevState));
         s.e_seen = __builtin_nan("");

@@ -278,7 +278,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     // same bits.  A shift is a common factor of all weights - W, ESS and log-MDD do not depend on it beyond rounding - but a lagged one does not
     // bound the weights by 1: should a stage's sums overflow (the cloud's largest energy grew by more than ~350 / (ϕ_n - ϕ_{n-1}) in one
     // mutation), the run goes on from that stage with the exact shift (below, at the batch's sync).  SMCMI_SHIFT_LAG=0: exact shifts from the
-    // start; =<k >= 3> (development): stage k's lagged shift is made to overflow.
+    // start; =<k >= 3> (development): stage k's lagged shift is made to overflow, =<-k>: to underflow.
     static const int lag_env = getenv("SMCMI_SHIFT_LAG") ? atoi(getenv("SMCMI_SHIFT_LAG")) : 1;
     bool shift_lag = !adaptive && lag_env != 0;
     // ---- per-handle set-up: run parameters and the stage-1 state in DevState (as engine 1), then imported into Ctl2
@@ -302,7 +302,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         rp.stall_on_exhaust = 1;
         rp.phi_rtol = rc->phi_rtol > 0.0 ? rc->phi_rtol : (rc->phi_rtol < 0.0 ? 0.0 : DEFAULT_PHI_RTOL);
         rp.stop_stage = rc->stop_after_stage > 0 ? rc->stop_after_stage : 0;
-        rp.shift_lag = shift_lag ? std::max(lag_env, 1) : 0;
+        rp.shift_lag = shift_lag ? (lag_env < 0 ? lag_env : std::max(lag_env, 1)) : 0;
         if (cont) {
             if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
             if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");

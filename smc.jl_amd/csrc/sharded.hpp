@@ -379,6 +379,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");
             if (s.stage != h0->h_st.stage) return set_err(SMCMI_ERR_STATE, "shards hold different loop states");
             s.rp = rp; s.done = 0; s.err = 0; s.skip_fold = 1; s.do_resample = 0;
+            s.e_seen = __builtin_nan("");                       // (as run1.hpp: this path keeps no Begin2::e_seen)
             if (push_state(h)) return SMCMI_ERR_HIP;
             continue;
         }

@@ -36,6 +36,34 @@ static int pull_state(smcmi_handle *h) {
     h->h_st.e_shift = 0.0;      // the energy shift belongs to a running stage chain (k_stage_begin): stand-alone calls that push this copy back are unshifted
     return 0;
 }
+// A cloud from outside replaces the one the handle learnt its largest energy from (stage2.hpp Begin2::e_seen, the lagged shift of fixed
+// schedules): the next begin takes the new cloud's own maximum, as after smcmi_set_loop_state.
+static int forget_e_seen(smcmi_handle *h) {
+    h->h_st.e_seen = __builtin_nan("");
+    HIP_TRY(hipMemcpyAsync(&h->d_st->e_seen, &h->h_st.e_seen, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+// The stand-alone calls (smcmi_correct, smcmi_ess_at, smcmi_solve_phi) are no part of a stage chain and have no energy maximum at hand: one
+// k_energy_max launch takes the cloud's - of the generalised energy of h->h_st.rp.pw / logp_old (kernels.hpp energy_base) - and the call shifts
+// by it like a stage does, so that it holds the reference's range (and more) instead of half of it.  Pushes h->h_st as the caller has set it
+// up, then sets e_shift in h->h_st and on the device.  The block maxima go through d_part_fin (2 nb_e doubles: the correction's own scratch,
+// written anew by every correction before it is read).
+static int standalone_shift(smcmi_handle *h, double *shift_out = nullptr) {
+    if (push_state(h)) return SMCMI_ERR_HIP;
+    const int nb = h->nb_e;
+    std::vector<double> m(nb, -__builtin_inf());
+    k_energy_max<<<nb, TB, 0, h->stream>>>(h->cl, h->d_st, h->d_part_fin);
+    HIP_TRY(hipMemcpyAsync(m.data(), h->d_part_fin, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    double e = -__builtin_inf();
+    for (double v : m) e = std::max(e, v);
+    h->h_st.e_shift = fabs(e) < 1e300 ? e : 0.0;              // no live particle with a finite energy: unshifted, as before
+    if (shift_out) *shift_out = h->h_st.e_shift;
+    HIP_TRY(hipMemcpyAsync(&h->d_st->e_shift, &h->h_st.e_shift, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
 static int push_model(smcmi_handle *h) {
     HIP_TRY(hipMemcpyAsync(h->d_model, &h->h_model, sizeof(ModelDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -338,7 +366,7 @@ extern "C" int smcmi_set_likelihood(smcmi_handle *h, int32_t which, int32_t fami
 extern "C" int smcmi_upload_cloud(smcmi_handle *h, const double *particles) {
     if (!h || !particles) return set_err(SMCMI_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (pull_state(h)) return SMCMI_ERR_HIP;
+    if (pull_state(h) || forget_e_seen(h)) return SMCMI_ERR_HIP;
     HIP_TRY(hipMemcpy(h->cl.buf[h->h_st.cur], particles, sizeof(double) * h->n * h->R, hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());          // (null-stream copy: not ordered with the handle's non-blocking stream)
     return 0;
@@ -346,7 +374,7 @@ extern "C" int smcmi_upload_cloud(smcmi_handle *h, const double *particles) {
 extern "C" int smcmi_upload_cloud_device(smcmi_handle *h, const double *dev_particles) {
     if (!h || !dev_particles) return set_err(SMCMI_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (pull_state(h)) return SMCMI_ERR_HIP;
+    if (pull_state(h) || forget_e_seen(h)) return SMCMI_ERR_HIP;
     // (the caller's pointer may be peer-device memory without peer access, or a misaligned view: the runtime's copy handles both)
     HIP_TRY(hipMemcpyAsync(h->cl.buf[h->h_st.cur], dev_particles, sizeof(double) * (size_t)h->n * h->R, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -489,6 +517,8 @@ extern "C" int smcmi_ess_at(smcmi_handle *h, const double *phis, int32_t k, doub
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (pull_state(h)) return SMCMI_ERR_HIP;
     DevState saved = h->h_st;
+    h->h_st.rp.pw = 0.0;                                          // (compute_ESS: always the prior_weight == 0 exponent, quirk Q4)
+    if (standalone_shift(h)) { h->h_st = saved; push_state(h); return SMCMI_ERR_HIP; }
     std::vector<double> tot(2 * KC);
     for (int base = 0; base < k; base += KC) {
         const int nv = std::min(KC, k - base);
@@ -519,6 +549,8 @@ extern "C" int smcmi_solve_phi(smcmi_handle *h, const double *sched, int32_t n_p
     s.rp.tempering_target = tempering_target; s.phi_n = phi_prev; s.phi_prop = *phi_prop; s.j = *j;
     s.resampled_last = *resampled_last; s.ess_prev = ess_prev;
     if (s.rp.phi_rtol <= 0.0) s.rp.phi_rtol = DEFAULT_PHI_RTOL;
+    s.rp.pw = 0.0;                                                // (the solver's exponent is the prior_weight == 0 one, quirk Q4)
+    if (standalone_shift(h)) { h->h_st = saved; push_state(h); return SMCMI_ERR_HIP; }      // (the stage begin below is given no maxima and keeps this shift)
     if (upload_sched(h, sched, n_phi) || push_state(h)) return SMCMI_ERR_HIP;
     k_stage_begin<<<1, BT, 0, h->stream>>>(h->d_st, h->d_sched, h->d_acc_part, 0, h->rec);
     // enough passes to walk the whole schedule in the worst case plus the bracketing passes
@@ -548,12 +580,14 @@ extern "C" int smcmi_correct(smcmi_handle *h, double phi_n, double phi_prev, dou
     s.stage = h->cfg.max_stages;   // records of a stand-alone call land in the last (scratch) slot
     s.rp.store_history = 0;
     s.sol[0].mode = MODE_FINAL; s.sol[0].phi_n = phi_n; s.sol[0].j = s.j; s.sol[0].phi_prop = s.phi_prop;
-    if (push_state(h)) return SMCMI_ERR_HIP;
+    double esh = 0.0;
+    if (standalone_shift(h, &esh)) { s = saved; push_state(h); return SMCMI_ERR_HIP; }
     k_pass<1, true><<<h->nb_e, TB, 0, h->stream>>>(h->cl, h->d_st, h->d_sched, nullptr, h->d_part_fin, h->nb_e, 0, nullptr, 0);
     k_post_correct<<<1, TB, 0, h->stream>>>(h->d_st, h->d_part_fin, h->nb_e, nullptr, h->rec, 0);
     k_normalize_weights<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, (double)h->cfg.n_parts);
     if (pull_state(h)) return SMCMI_ERR_HIP;
-    out->ess = s.ess; out->sum_unnorm = s.sumw; out->logz_inc = s.logz; out->resample = s.do_resample;
+    // (the sums are the shifted ones: Σ W w̃ gets its common factor back - it leaves the FP64 range where the reference's own sum does)
+    out->ess = s.ess; out->sum_unnorm = s.sumw * exp((phi_n - phi_prev) * esh); out->logz_inc = s.logz; out->resample = s.do_resample;
     const int err = s.err;
     s = saved;
     if (push_state(h)) return SMCMI_ERR_HIP;

@@ -564,8 +564,8 @@ __device__ inline int begin2_wave(int n, const Post2 &po, const RunParams &rp, c
     // fixed schedules, RunParams::shift_lag: the shift is the maximum the PREVIOUS begin learnt (any common shift leaves W, ESS and log-MDD
     // what they are up to rounding; this one is known before stage n - 1's mutation rows are: stage n's correction can ride them)
     // (development, SMCMI_SHIFT_LAG=<k >= 3>: stage k's lagged shift is lowered by 1e6 - mathematically neutral, but its sums overflow: the
-    // fallback to exact shifts, run2.hpp, under test)
-    if (fixed && rp.shift_lag && fabs(po.e_seen) < 1e300) b.e_shift = po.e_seen - (rp.shift_lag == n ? 1e6 : 0.0);
+    // fallback to exact shifts, run2.hpp, under test; =<-k>: raised by 1e6 - its squares underflow)
+    if (fixed && rp.shift_lag && fabs(po.e_seen) < 1e300) b.e_shift = po.e_seen - (rp.shift_lag == n ? 1e6 : (rp.shift_lag == -n ? -1e6 : 0.0));
     b.e_center = po.e_center;
     if (fixed) {
         b.phi_n = (n <= n_phi) ? sched[n - 1] : 1.0;
@@ -761,7 +761,7 @@ static __global__ void __launch_bounds__(T1) k2_pass(CloudPtrs cl, DevState *st,
     __shared__ Solver S;
     __shared__ int s_flag;
     const int bstage = ctl->bg.stage, bfinal = ctl->bg.final;
-    const double phi_prev = ctl->bg.phi_prev, esh = st->rp.pw == 0.0 ? ctl->bg.e_shift : 0.0;
+    const double phi_prev = ctl->bg.phi_prev, esh = ctl->bg.e_shift;
     if (bstage != n || bfinal) return;
     solver_prologue2(st, sched, prev, p, &S, s_vt, s_tot, s_srt, 0, &s_flag, T1);
     if (s_flag) {                                         // an error (the objective is NaN at the walk's end: fzero's bracket error, helpers.jl:49-50)
@@ -1074,7 +1074,7 @@ __global__ void __launch_bounds__(T1) k2_correct(CloudPtrs cl, DevState *st, Ctl
         __syncthreads();
         if (s_bg.stage != n || !s_bg.final || s_po.stage != n - 1) return;
     }
-    const double phi = s_bg.phi_n, phi_prev = s_bg.phi_prev, esh = pw == 0.0 ? s_bg.e_shift : 0.0;
+    const double phi = s_bg.phi_n, phi_prev = s_bg.phi_prev, esh = s_bg.e_shift;
     const double *sh = s_po.shift;           // read from LDS where used (uniform address): twenty registers the accumulators need
     const double unshift = hist ? exp((phi - phi_prev) * esh) : 1.0;                      // history keeps the true exp(δ e)
     if constexpr (D <= 10) {
@@ -1136,8 +1136,13 @@ __device__ inline int decide2(const Begin2 &bg, double threshold, double phi_rto
         if (!verified) return 4;
     }
     // check_nan_ess, helpers.jl:270-305 (sums that overflowed count as well: under a lagged energy shift - Begin2::e_seen - a cloud whose
-    // largest energy grew by more than ~350 / (ϕ_n - ϕ_{n-1}) in ONE mutation overflows Σ W̃²; the host then redoes the stage with the exact shift)
-    if (isnan(ess) || fabs(s1) > 1.7e308 || fabs(s2) > 1.7e308) return SMCMI_ERR_NAN_ESS;
+    // largest energy grew by more than ~350 / (ϕ_n - ϕ_{n-1}) in ONE mutation overflows Σ W̃²; the host then redoes the stage with the exact shift.
+    // The other side: a shift ABOVE the cloud's largest energy by G / (ϕ_n - ϕ_{n-1}) scales every W̃ by exp(-G), and the squares leave the
+    // normal range long before anything is NaN - ESS off by 2.5e-9 at G = 365, by 0.65 % at 370, twice its value at 372 and +inf (s2 == 0: "no resample") from 373.
+    // A square below 2^-1022 is rounded at 2^-1075: with s2 >= 1e-290 the N of them together are below N 2.5e-34 of s2; a smaller s2 is the
+    // fallback's case as well.  Under an exact shift the particle with the largest energy keeps its weight W, s2 >= W².)
+    // (ESS <= N: an infinite one is s1² or s2 out of range with both sums still finite - from G = -350 on the overflow side)
+    if (!(ess <= 1.7e308 && s2 >= 1e-290 && s2 <= 1.7e308)) return SMCMI_ERR_NAN_ESS;
     return ess < threshold ? 1 : 0;
 }
 
@@ -1583,7 +1588,7 @@ __device__ inline void post2(int n, const Begin2 &bg, const Post2 &po, const Run
     Post2 p = po;
     p.stage = n; p.j = bg.j; p.resampled_last = rs; p.do_resample = rs; p.resamples = po.resamples + rs; p.fold_valid = 1;
     p.phi_n = bg.phi_n; p.phi_prop = bg.phi_prop; p.ess = ess; p.sumw = s1; p.sumw2 = s2;
-    const double dlz = (bg.phi_n - bg.phi_prev) * (rp.pw == 0.0 ? bg.e_shift : 0.0);      // log of the common factor the shifted weights left out
+    const double dlz = (bg.phi_n - bg.phi_prev) * bg.e_shift;      // log of the common factor the shifted weights left out
     p.logz = po.logz + (log(s1 / (double)rp.n_parts) + dlz);
     p.c = po.c * bg.cfac;
     p.accept = a; p.e_center = bg.e_center; p.e_shift = bg.e_shift; p.e_seen = bg.e_seen;
@@ -1972,10 +1977,10 @@ SMCMI_FP_CONTRACT
 // coh: the row is totalled inside this launch (Tail2 / stage3.hpp).  All threads call; starts and ends with a barrier.
 template <int T, class ST>
 __device__ inline void k2_mut_row_f(bool adaptive, double like, double like_prev, double w_part, double acc_val, double e_center, bool live,
-                                    bool rs, double *scratch, double *red, ST store) {
+                                    bool rs, double *scratch, double *red, ST store, double e_base) {
     const int tid = threadIdx.x;
     __syncthreads();
-    double em = energy_or_ninf(like, like_prev, rs ? 1.0 : w_part, live);
+    double em = energy_or_ninf(like, e_base, rs ? 1.0 : w_part, live);      // (e_base: kernels.hpp energy_base - like_prev itself unless a prior weight is set)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) em = fmax(em, __shfl_xor(em, off, 64));
     __shared__ double emx[T / 64];
@@ -2007,8 +2012,8 @@ __device__ inline void k2_mut_row_f(bool adaptive, double like, double like_prev
 }
 template <int T>
 __device__ inline void k2_mut_row(double *row, bool adaptive, double like, double like_prev, double w_part, double acc_val, double e_center, bool live,
-                                  bool rs, double *scratch, double *red, bool coh) {
-    k2_mut_row_f<T>(adaptive, like, like_prev, w_part, acc_val, e_center, live, rs, scratch, red, [&](int idx, double v) { row_store(row + idx, v, coh); });
+                                  bool rs, double *scratch, double *red, bool coh, double e_base) {
+    k2_mut_row_f<T>(adaptive, like, like_prev, w_part, acc_val, e_center, live, rs, scratch, red, [&](int idx, double v) { row_store(row + idx, v, coh); }, e_base);
 }
 
 // K2.  The mutation body is k_mutate_reg's (src/mutation.jl:56-138, helpers.jl:87-164; same arithmetic in the same order), fed
@@ -2121,7 +2126,7 @@ SMCMI_FP_CONTRACT
     }
     // ---- this block's row for the next stage's begin: energy power sums (adaptive schedules), Σ accept, energy maximum
     k2_mut_row<T>(ma.rows_mut + (long long)blockIdx.x * RMUT, ma.adaptive != 0, like, like_prev, w_part, acc_val, e_center, live, rs != 0, l_dat, red,
-                  TAIL && ma.tail.tick != nullptr);
+                  TAIL && ma.tail.tick != nullptr, energy_base(like_prev, st->rp.pw, st->rp.logp_old));
     K2_STAMP(ma.prof, 10);
     if constexpr (TAIL) tail_reduce<T>(ma.tail, ma.rows_mut, (int)blockIdx.x / g.nb2, g.nb2, RMUT, RMAX_IDX, T == 256 ? 1 : 0);
     if (blockIdx.x == 0 && !ma.pre) k2_bookkeeping<D, T>(st, ctl, ma, L, &S, rs);
@@ -2192,7 +2197,7 @@ __global__ void __launch_bounds__(256, 1) k2w_mutate(CloudPtrs cl, DevState *st,
     }
     // ---- this block's row for the next stage's begin (the per-particle vectors are dead: their area is the reduction's scratch)
     k2_mut_row<TB2>(ma.rows_mut + (long long)blockIdx.x * RMUT, ma.adaptive != 0, like, like_prev, counted ? w_part : 0.0, counted ? acc_val : 0.0, e_center, counted,
-                    rs != 0, gen, L.red, ma.tail.tick != nullptr);
+                    rs != 0, gen, L.red, ma.tail.tick != nullptr, energy_base(like_prev, st->rp.pw, st->rp.logp_old));
     tail_reduce<TB2>(ma.tail, ma.rows_mut, vl, g.nb2, RMUT, RMAX_IDX, 0);
     if (blockIdx.x == 0) k2_bookkeeping<D, TB2>(st, ctl, ma, L, &S, rs);
 }

@@ -146,7 +146,7 @@ SMCMI_FP_CONTRACT
     // ---- this block's row for the next stage's begin; the last block of a virtual shard totals the shard's rows - all groups of 64 rows
     // in ONE batch of loads (RMUT columns: seven groups fit the block) - and posts them
     k2_mut_row<T>(ma.rows_mut + (long long)blockIdx.x * RMUT, ma.adaptive != 0, like, like_prev, w_part, acc_val, e_center, live, rs != 0, l_dat, red,
-                  ma.tail.tick != nullptr);
+                  ma.tail.tick != nullptr, energy_base(like_prev, st->rp.pw, st->rp.logp_old));
     K2_STAMP(ma.prof, 10);
     tail_reduce<T, RMUT>(ma.tail, ma.rows_mut, (int)blockIdx.x / g.nb2, g.nb2, RMUT, RMAX_IDX, 0);
     K2_STAMP(ma.prof, 11);

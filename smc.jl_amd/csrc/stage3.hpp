@@ -1203,7 +1203,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         if (!entered && !(RIDE && !first && !rides)) {          // (riding: the stage that ends the launch forms no row - its begin, next, says so)
             // (riding: what begin2_wave will put into Begin2 for a fixed schedule under shift_lag - the same values, before the begin has run)
             const double phi = rides ? (n <= rp.n_phi ? sa.sched[n - 1] : 1.0) : s_a.bg.phi_n, phi_prev = rides ? po.phi_n : s_a.bg.phi_prev;
-            const double esh = pw == 0.0 ? (rides ? po.e_seen - (rp.shift_lag == n ? 1e6 : 0.0) : s_a.bg.e_shift) : 0.0;
+            const double esh = rides ? po.e_seen - (rp.shift_lag == n ? 1e6 : (rp.shift_lag == -n ? -1e6 : 0.0)) : s_a.bg.e_shift;
             K3_CHUNKS_BEGIN                                     // (two chunks: the one in registers, then the parked one - which stays in registers for the MH step)
             unsigned long long *my_cm = sa.g_cm + K3_RPAR(n) + (long long)rowi * MCM * 2;
             K3_V_RESET();
@@ -1366,7 +1366,8 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             double *plain = ma.rows_mut + (long long)rowi * RMUT;      // (the launch after this one totals the last stage's rows from here)
             unsigned long long *my_mut = sa.g_mut + K3_RPAR(n) + (long long)rowi * RMUT * 2;
             k2_mut_row_f<T3>(ma.adaptive != 0, like, like_prev, live ? Wt : 0.0, live ? acc_val : 0.0, e_center, live, rs != 0, red, L.red,
-                             [&](int idx, double val) { if (K3_HAS) { gran_store(my_mut + idx * 2, val, tag); plain[idx] = val; } });
+                             [&](int idx, double val) { if (K3_HAS) { gran_store(my_mut + idx * 2, val, tag); plain[idx] = val; } },
+                             energy_base(like_prev, rp.pw, rp.logp_old));
             if (K3_HAS && tid == RMUT - 1) gran_store(my_mut + tid * 2, 0.0, tag);                  // (column 33 is unused)
         }
         K3_CHUNKS_END
