@@ -892,9 +892,16 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     Ctl2 c{};
     const auto t0 = std::chrono::steady_clock::now();
     bool finished = false;
+    // one handle, predictions on, selection in place: behind the two certificate stages every stage of the run belongs to ONE segment, which
+    // leaves by itself at ϕ = 1, at a stall or at capacity - nothing enqueued behind it is wasted, so the batch runs to `room` instead of
+    // cutting the segment in two at a host sync (a write-back, a reload and a prologue of the cloud around ~50 µs of idle GPU).  A batch that
+    // stalled falls back to the doubling batches until one passes without a stall.
+    const bool whole_run_batches = adaptive && e3 && sel_inside && predict_select && sel_mode == 0 && rc->sync_every <= 0 && g.hs.size() == 1 && !seg_sys;
+    bool last_stalled = false;
     while (!finished) {
         const int room = max_iter - launched;
-        const int batch = adaptive ? std::min(std::min(spec_on || !spec_ok ? cur_sync : std::min(cur_sync, cert_sync), std::max(stages_left_est, 4)), room) : room;
+        const bool to_room = whole_run_batches && spec_on && !last_stalled && force_sel < 0;
+        const int batch = adaptive && !to_room ? std::min(std::min(spec_on || !spec_ok ? cur_sync : std::min(cur_sync, cert_sync), std::max(stages_left_est, 4)), room) : room;
         bool stalled = false;
         int seg_a = -1, seg_b = -1;                      // pending segment of engine 3
         bool seg_enter = false, seg_sel = false;         // ... which enters at the mutation of its first stage (corrected / resampled by launches)
@@ -1054,6 +1061,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             stages_left_est = left < 1e6 ? (int)left + 1 : 1 << 30;
         }
         if (predict_select) { pred_ess = p.ess; pred_rl = p.do_resample; }
+        last_stalled = stalled;
         if (rc->sync_every <= 0) cur_sync = stalled ? sync_every : std::min(2 * cur_sync, 4 * sync_every);
         if (!spec_on && spec_ok) cert_sync = stalled ? 8 : std::min(2 * cert_sync, sync_every);
     }

@@ -1604,6 +1604,7 @@ struct Prop2 {                 // LDS pointers (k2_mutate carves them out of its
     int *bfree, *bptr, *fi;
     double *Lraw, *logdet, *mub, *sdd, *sdn;
     int *ball, *loff;
+    double *Ls;                // A1F_LS only: the padded, transposed factor the α = 1 MH step reads (Mut2Lds::Ls), else unused
 };
 // chol_rows_in_regs with the dimension as a compile-time constant: straight-line code the scheduler can overlap across columns
 template <int DB>
@@ -1637,9 +1638,35 @@ __device__ inline int shuffle_partner(unsigned long long seed, unsigned stage, i
     return jx;
 }
 
+// Fisher-Yates (helpers.jl:216: i = nf-1 .. 1, swap(i, j_i)) without a serial pass over memory, by ONE wavefront: lane l traces position l
+// back through the swaps in reverse order of application; what it ends at is the identity's entry that lands on l.  jx: shuffle_partner()
+// of the lane.  Leaves the shuffled free set and the block pointers; depends on (seed, stage, nf, nb) only.
+__device__ inline void shuffle_trace(int jx, int lane, int nf, int nb, int *bfree, int *bptr) {
+    int pos = lane;
+    for (int i = 1; i < nf; ++i) {
+        const int ji = __shfl(jx, i, 64);
+        pos = pos == i ? ji : (pos == ji ? i : pos);
+    }
+    if (lane < nf) bfree[lane] = pos;
+    const int sub = (nf + nb - 1) / nb;
+    if (lane < nb) bptr[lane] = lane * sub;
+    if (lane == nb) bptr[nb] = nf;
+}
+
+// The α = 1 fast path of proposal2 / k2_mh_steps (the segment kernel's α = 1 variants, stage3.hpp): work an α = 1 stage never needs, or
+// that need not sit between the correction totals and the MH step, is left out or moved.  Compile-time bits:
+constexpr int A1F_SHUF = 1;    // the caller has run shuffle_trace (P.bfree, P.bptr) in front of its wait for the totals
+constexpr int A1F_NOMIX = 2;   // no mixture scales (mub, sdd, sdn: mix_expand's, α < 1 only)
+constexpr int A1F_LOGDET = 4;  // no log-determinant here: every wavefront of the MH step forms it from the factor's diagonal (k2_mh_steps)
+constexpr int A1F_LS = 8;      // one random block: the Cholesky wavefront stores its rows where the MH step reads them (P.Ls), no expansion there
+#ifndef SMCMI_A1FAST
+#define SMCMI_A1FAST (A1F_SHUF | A1F_NOMIX | A1F_LOGDET | A1F_LS)
+#endif
+
 // jx_pre: shuffle_partner() of lane (threadIdx.x & 63), valid in wavefront 1 (threads 64..127)
 // CHM: rows of the in-register Cholesky (12 serves n_para <= 12; 16 the wide kernels)
-template <int CHM = 12>
+// FAST: A1F_* bits (0: everything here, for every kind of proposal)
+template <int CHM = 12, int FAST = 0>
 __device__ inline bool proposal2(const double *T, const double *shift, int d, int nf, int nb, double c, unsigned long long seed,
                                  unsigned stage, const Prop2 &P, int *s_fail, int TT, int jx_pre, long long *prof = nullptr, long long *prof_any = nullptr) {
     const int t = threadIdx.x, da = d + 1;
@@ -1653,21 +1680,11 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
         P.covl[e] = T[p] / sw - (T[a + 1] / sw) * (T[b + 1] / sw);
     }
     for (int a = t; a < d; a += TT) P.mean[a] = shift[a] + T[a + 1] / sw;
-    if (t >= 64 && t < 128) {            // wave 1 shuffles while the others finish the covariance
-        // Fisher-Yates (helpers.jl:216: i = nf-1 .. 1, swap(i, j_i)) without a serial pass over memory: lane l traces position l
-        // back through the swaps in reverse order of application; what it ends at is the identity's entry that lands on l.
-        const int i0 = t - 64;
-        const int jx = jx_pre;
-        int pos = i0;
-        for (int i = 1; i < nf; ++i) {
-            const int ji = __shfl(jx, i, 64);
-            pos = pos == i ? ji : (pos == ji ? i : pos);
-        }
-        if (i0 < nf) P.bfree[i0] = pos;
-        const int sub = (nf + nb - 1) / nb;
-        if (i0 < nb) P.bptr[i0] = i0 * sub;
-        if (i0 == nb) P.bptr[nb] = nf;
+    if constexpr (!(FAST & A1F_SHUF)) {
+        if (t >= 64 && t < 128) shuffle_trace(jx_pre, t - 64, nf, nb, P.bfree, P.bptr);      // wave 1 shuffles while the others finish the covariance
     }
+    // (one block: every entry of Ls the Cholesky wavefront will not store is zero - nobody reads Ls between the previous MH step and the next)
+    if constexpr ((FAST & A1F_LS) != 0) { if (nb == 1) for (int e = t; e < d * d; e += TT) P.Ls[e] = 0.0; }
     __syncthreads();
     K2_STAMP(prof, 4);
     K3_STAMP_ANY(prof_any, 0);
@@ -1675,11 +1692,13 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
     auto sig = [&](int f, int g2) { const int a = P.fi[f], b = P.fi[g2]; return (P.covl[a * d + b] + P.covl[b * d + a]) / 2.0; };
     for (int i = t; i < nf; i += TT) {
         const int f = P.bfree[i];
-        const double sff = sig(f, f);
+        [[maybe_unused]] const double sff = sig(f, f);
         P.ball[i] = P.fi[f];
-        P.mub[i] = P.mean[P.fi[f]];
-        P.sdd[i] = sqrt(c * c * sff);
-        P.sdn[i] = sqrt(sff);
+        if constexpr (!(FAST & A1F_NOMIX)) {
+            P.mub[i] = P.mean[P.fi[f]];
+            P.sdd[i] = sqrt(c * c * sff);
+            P.sdn[i] = sqrt(sff);
+        }
     }
     {
         const int sub = (nf + nb - 1) / nb;          // every block but the last has `sub` entries: block b's matrix starts at b sub²
@@ -1710,18 +1729,30 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
                 else ok = chol_rows_in_regs<12, true>(r, db, lane);
             } else ok = chol_rows_in_regs<CHM, true>(r, db, lane);
             if (!ok && lane == 0) *s_fail = 1;
+            if constexpr ((FAST & A1F_LS) != 0) {
+                if (nb == 1) {                      // row `lane` of L is column ball[lane] of the transposed, padded form: Ls[k][ball[lane]] = L[lane][k]
+                    const int col = lane < db ? P.ball[lane] : 0;
+#pragma unroll
+                    for (int k = 0; k < CHM; ++k)
+                        if (lane < db && k <= lane) P.Ls[k * d + col] = r[k];
+                }
+            }
 #pragma unroll
             for (int k = 0; k < CHM; ++k)
                 if (lane < db && k < db) P.Lraw[off + lane * db + k] = k <= lane ? r[k] : 0.0;
-            double dg = 1.0;                        // own diagonal entry L[lane][lane]
+            if constexpr ((FAST & A1F_LOGDET) != 0) {
+                if (lane == 0) P.loff[b] = off;
+            } else {
+                double dg = 1.0;                        // own diagonal entry L[lane][lane]
 #pragma unroll
-            for (int k = 0; k < CHM; ++k) dg = (k == lane) ? r[k] : dg;
-            const double lg = (lane < db) ? log(dg) : 0.0;
-            double ld = 0.0;
+                for (int k = 0; k < CHM; ++k) dg = (k == lane) ? r[k] : dg;
+                const double lg = (lane < db) ? log(dg) : 0.0;
+                double ld = 0.0;
 #pragma unroll
-            for (int i = 0; i < CHM; ++i)
-                if (i < db) ld += bcast_lane(lg, i);
-            if (lane == 0) { P.logdet[b] = 2.0 * ld; P.loff[b] = off; }
+                for (int i = 0; i < CHM; ++i)
+                    if (i < db) ld += bcast_lane(lg, i);
+                if (lane == 0) { P.logdet[b] = 2.0 * ld; P.loff[b] = off; }
+            }
         }
     }
     __syncthreads();
@@ -1873,7 +1904,10 @@ __device__ inline void k2_stage_lik(const LikDev &ld0, const LikDev &ld1, double
 // persistent segment kernel (stage3.hpp) share - same arithmetic in the same order.  The proposal's arrays are in LDS (L.Lraw,
 // L.logdet_s, L.mub_raw, L.sdd_raw, L.sdn_raw, L.ball_raw, L.bptr_s, L.loff_s), published by a barrier before the call; proposal 0's
 // random numbers may arrive in (step_prob, uc, z) (PREDRAW, or ma.zbuf).  ldz: leading dimension of ma.zbuf.  All threads call.
-template <int D, bool ALPHA1, int T, bool PREDRAW, bool ZPART = false>
+// FAST (α = 1 only): A1F_LS - with one block L.Ls holds the expanded factor already (proposal2<.., FAST>); A1F_LOGDET - L.logdet_s is not
+// written: each wavefront forms the block's log-determinant from the diagonal of L.Lraw, the operations of proposal2 in their order (log of
+// each diagonal entry, added in ascending index from 0.0, times 2)
+template <int D, bool ALPHA1, int T, bool PREDRAW, bool ZPART = false, int FAST = 0>
 __device__ inline void k2_mh_steps(const Mut2Lds<D> &L, double *mixbuf, int *mixpos, double *mixzt, const Mut2Args &ma, long long ldz,
                                    const LikView (&lv)[2], const ModelView &mv, int nb, int nf, bool live, long long i, unsigned long long pid,
                                    unsigned stage, double phi_n, double (&x)[D], double &like, double &lprior, double &like_prev, double &accept,
@@ -1891,7 +1925,7 @@ SMCMI_FP_CONTRACT
         for (int b = 0; b < nb; ++b) {
             if ((nb > 1 || step == 0) && (step | b) != 0) __syncthreads();   // previous block's readers (the prologue ends with a barrier)
             const int p0 = bptr_s[b], db = bptr_s[b + 1] - p0;
-            if (nb > 1 || step == 0) {              // expand this block's constants to the padded D x D form
+            if ((nb > 1 || step == 0) && !((FAST & A1F_LS) != 0 && nb == 1)) {              // expand this block's constants to the padded D x D form
                 const double *Lb = Lraw + loff_s[b];
                 if constexpr (ALPHA1) {
                     for (int e = tid; e < D * D; e += T) Ls[e] = 0.0;
@@ -1903,6 +1937,17 @@ SMCMI_FP_CONTRACT
                 } else
                     mix_expand<D, T>(MX, Lb, Wraw + loff_s[b], ball_raw + p0, mub_raw + p0, sdd_raw + p0, sdn_raw + p0, db, logdet_s[b], tid);
                 __syncthreads();
+            }
+            [[maybe_unused]] double logdet_w = 0.0;
+            if constexpr (ALPHA1 && (FAST & A1F_LOGDET) != 0) {
+                const int lane = tid & 63;
+                const double lg = (lane < db) ? log(Lraw[loff_s[b] + lane * db + lane]) : 0.0;
+                double ld = 0.0;
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+                    if (i < db) ld += bcast_lane(lg, i);
+                logdet_w = 2.0 * ld;
+                asm volatile("" : "+v"(logdet_w));       // (a value as loaded from LDS: its doubling is not contracted into the sum that reads it)
             }
             if (!live) continue;
             const unsigned t = (unsigned)(step * nb + b);
@@ -1922,7 +1967,9 @@ SMCMI_FP_CONTRACT
                 double zz2 = 0.0;
 #pragma unroll
                 for (int e = 0; e < D; ++e) zz2 += z[e] * z[e];
-                q1 = (-((double)db * LOG2PI + logdet_s[b] + zz2) / 2.0 < -745.1332191019412) ? __builtin_nan("") : 0.0;
+                double logdet_b;
+                if constexpr ((FAST & A1F_LOGDET) != 0) logdet_b = logdet_w; else logdet_b = logdet_s[b];
+                q1 = (-((double)db * LOG2PI + logdet_b + zz2) / 2.0 < -745.1332191019412) ? __builtin_nan("") : 0.0;
                 double sacc[D];
 #pragma unroll
                 for (int k = 0; k < D; ++k) { xo[k] = x[k]; sacc[k] = 0.0; }

@@ -926,6 +926,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     __shared__ double mixzt[ALPHA1 ? 1 : T3 * D];
     Mut2Lds<D> L(sm);
     const int tid = threadIdx.x;
+    constexpr int FAST = ALPHA1 ? (SMCMI_A1FAST) : 0;           // proposal2's α = 1 fast path (stage2.hpp A1F_*)
 #ifdef SMCMI_K3_CH2
     const int W = g.Vl * ((g.nb2 + CH - 1) / CH);               // (workers per virtual shard: every one owns CH blocks of it)
 #else
@@ -1256,6 +1257,9 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         if (act != 0) break;
         const double e_center = s_a.bg.e_center;
         const int jx_pre = (tid >= 64 && tid < 128) ? shuffle_partner(ma.seed, (unsigned)n, tid - 64, nf) : 0;     // (before the totals exist)
+        // (α = 1: so is the shuffle itself - L.bfree and this stage's block pointers are idle since the previous stage's proposal; a selection
+        // in between uses neither.  proposal2's first barrier publishes them)
+        if constexpr ((FAST & A1F_SHUF) != 0) { if (tid >= 64 && tid < 128) shuffle_trace(jx_pre, tid - 64, nf, nb, L.bfree, L.bptr_s); }
         // ---- the V shard totals -> decision (smc_main.jl:427-455) -> proposal (smc_main.jl:457-465, helpers.jl:215-260, mutation.jl:81)
         if (!entered && !(RIDE && rides) && !(rows_two ? gather_totals<2>(sa.g_cm + K3_RPAR(n), g.V, MCM, -1, tag, sa.to, &s_to, s_tot, s_vt)
                                    : gather_totals(rows_direct ? sa.g_cm + K3_RPAR(n) : sa.gt_cm + K3_TPAR(n), g.V, MCM, -1, tag, sa.to, &s_to, s_tot, s_vt, sys))) { timed_out = true; break; }
@@ -1320,8 +1324,8 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         }
         if (tid == T3 - 64) post2(n, s_a.bg, po, rp, s_tot[0], s_tot[1], ess, rs, &B.po);       // (the last wavefront: its logarithm runs beside the covariance and the shuffle of wavefronts 0 and 1)
         {
-            Prop2 P{L.covl, L.Aw, L.mean_s, L.bfree, L.bptr_s, L.fi, L.Lraw, L.logdet_s, L.mub_raw, L.sdd_raw, L.sdn_raw, L.ball_raw, L.loff_s};
-            if (!proposal2(s_tot + 2, po.shift, D, nf, nb, po.c * s_a.bg.cfac, ma.seed, (unsigned)n, P, &s_fail, T3, jx_pre, nullptr,
+            Prop2 P{L.covl, L.Aw, L.mean_s, L.bfree, L.bptr_s, L.fi, L.Lraw, L.logdet_s, L.mub_raw, L.sdd_raw, L.sdn_raw, L.ball_raw, L.loff_s, L.Ls};
+            if (!proposal2<12, FAST>(s_tot + 2, po.shift, D, nf, nb, po.c * s_a.bg.cfac, ma.seed, (unsigned)n, P, &s_fail, T3, jx_pre, nullptr,
                            (sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr)) {
                 // PosDefException aborts the run (mutation.jl:81).  The gatherers build no proposal and would wait for mutation rows that
                 // never come: the writer raises the waits' abort word (every bounded wait polls it), so they leave at once
@@ -1358,7 +1362,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             Wt = rs ? 1.0 : (v * nrm_N) / nrm_sumw;             // W·N then /ΣW̃, two roundings like the reference (particle.jl:362-366); 1 after a resample
             if (ma.hist_W && ma.store_history) ma.hist_W[(long long)(n - 1) * ma.hist_ld + i] = Wt;
         }
-        k2_mh_steps<D, ALPHA1, T3, true>(L, mixbuf, mixpos, mixzt, ma, g.n, lv, mv, nb, nf, live, i, pid, (unsigned)n, phi_n, x, like, lprior, like_prev, accept,
+        k2_mh_steps<D, ALPHA1, T3, true, false, FAST>(L, mixbuf, mixpos, mixzt, ma, g.n, lv, mv, nb, nf, live, i, pid, (unsigned)n, phi_n, x, like, lprior, like_prev, accept,
                                          step_prob, uc, z);
         if (live) acc_val = accept / (double)nf;                // quirk Q2: normalised by n_free only
         K3_STAMP(sa.prof, 5);
