@@ -211,7 +211,8 @@ int smcmi_bridge_resample(smcmi_handle *dst, smcmi_handle *src, int32_t method, 
                           const double *offsets, int64_t *ancestors_out);
 int smcmi_copy_rows(smcmi_handle *dst, int64_t dst_row0, smcmi_handle *src, int64_t src_row0, int64_t n_rows);
 int smcmi_normalize_weights(smcmi_handle *h, int32_t zero_bad_loglh);
-int smcmi_cloud_device_ptr(smcmi_handle *h, double **dev_ptr, int64_t *ld); /* current buffer, for zero-copy hosts */
+/* current buffer, for zero-copy hosts.  The pointer is writable: the handle treats the call like an upload (the next moments are centred on the cloud). */
+int smcmi_cloud_device_ptr(smcmi_handle *h, double **dev_ptr, int64_t *ld);
 
 /* ---- stage primitives (same kernels smcmi_run launches) --------------------------------------- */
 /* compute_ESS(loglh, weights, ϕ, ϕ_n1; old_loglh) for k candidate ϕ (helpers.jl:173-181) */
@@ -228,6 +229,9 @@ int smcmi_correct(smcmi_handle *h, double phi_n, double phi_prev, double prior_w
 int smcmi_resample(smcmi_handle *h, int32_t method, uint32_t stage, const double *offsets, int64_t *ancestors_out);
 /* weighted_mean / weighted_cov (particle.jl:481-483, 526-529); cov row-major d x d */
 int smcmi_moments(smcmi_handle *h, double *mean, double *cov);
+/* parity aid: the weighted mean and covariance the last stage of a run used for its proposals (or the last smcmi_moments returned), as every
+   engine leaves them in the handle's state; cov row-major d x d, before the symmetrisation (R + R') / 2.  Copies, launches nothing. */
+int smcmi_debug_stage_moments(smcmi_handle *h, double *mean, double *cov);
 /* all particles' mutation() (mutation.jl:56-138, smc_main.jl:472-484); mu_free/Sigma_free are θ̄_fr, R_fr;
    blocks 0-based: block b = block_idx[block_ptr[b] .. block_ptr[b+1]) over free-parameter positions */
 int smcmi_mutate(smcmi_handle *h, const double *mu_free, const double *Sigma_free, const int32_t *block_ptr,

@@ -308,6 +308,7 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     }
     const int base = cont ? s.stage - 1 : 0;
     if (push_state(h)) return SMCMI_ERR_HIP;
+    if (int e = center_single(h, !cont)) return e;
     if (!cont) {
         const double v0[4] = {0.0, rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts, rc->c, rc->target};
         HIP_TRY(hipMemcpyAsync(h->rec.phi, &v0[0], sizeof(double), hipMemcpyHostToDevice, h->stream));

@@ -57,7 +57,8 @@ struct Eng2 {
     int z_ahead = 0;                 // large shards: proposals per particle the drawing blocks of K1 leave in zbuf (0 with rng_ahead: all of them)
 };
 
-static const int ESUM_RED_ROWS = 128;         // rows left by the first level of the energy-sum reduction when there are very many blocks
+static const int CENTER_SLOTS = 64;           // shards a group can gather the centre of its cloud over (sharded.hpp MAX_SHARDS)
+static const int ESUM_RED_ROWS = 128;        // rows left by the first level of the energy-sum reduction when there are very many blocks
 struct smcmi_handle {
     smcmi_config cfg{};
     int d = 0, R = 0, npairs = 0;
@@ -83,6 +84,11 @@ struct smcmi_handle {
     double *d_part_mom = nullptr, *d_totals = nullptr, *d_acc_part = nullptr, *d_esum_part = nullptr, *d_esum_red = nullptr, *d_emax_part = nullptr, *d_zbuf = nullptr, *d_comm = nullptr, *d_offsets = nullptr;
     long long comm_cap = 0;
     double *d_hist_w = nullptr, *d_hist_W = nullptr;
+    // centre of the one-pass moments at the head of a chain (kernels.hpp k_center_*): CENTER_SLOTS rows of 2 d + 1 doubles (one per shard),
+    // the shift and its "apply" word (d + 1), nb_c block rows of 2 d
+    double *d_center = nullptr;
+    int nb_c = 0;
+    bool center_stale = true;        // the cloud came from outside since DevState::shift was last set (create, upload, prior draw, row copies)
     std::vector<double> lik_host_data[2], lik_host_aux[2];   // host copies (lgss_kalman only): is the old vintage a prefix of the new one?
     // peer mailbox of sharded engine-2 runs (stage2.hpp Mailbox): this handle's table, the peers' tables as mapped here
     unsigned long long *d_mbox = nullptr;

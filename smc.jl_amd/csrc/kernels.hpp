@@ -1611,6 +1611,93 @@ __device__ inline void moments_from_totals(DevState *st, const double *totals, i
 static __global__ void __launch_bounds__(64) k_finalize_moments(DevState *st, const double *totals, int d) {
     moments_from_totals(st, totals, d, threadIdx.x, 64);
 }
+
+// ---- the shift at the head of a chain.  The one-pass sums above are exact enough only while the shift lies within the cloud: T[p] / sw -
+// m_a m_b loses (distance / σ)² ulps.  Inside a chain the previous stage's mean is such a shift; at its head (a run's first moments, the
+// first after a cloud came from outside, the first stand-alone smcmi_moments) nothing is known, so the cloud is asked: per column the
+// smallest and largest finite value over the particles with a positive weight.  Minima and maxima are exact and do not depend on the order
+// they are taken in, so every engine, every grid and every shard count derives the same shift, bit for bit.  A column keeps shift 0 while
+// 0 is no further from the midrange than a quarter of the range (0 is then within 3/4 of the range of the mean, the midrange within 1/2:
+// nothing to gain, and runs from priors centred near 0 keep the bits they had); otherwise it is centred on the midrange.
+// k_center_probe: block rows of (-min, max) per column.
+// (the scan and the rule exist once: one handle and a group of any size must derive the same shift, bit for bit)
+// this block's row of (-min, max) per column over its chunk of the cloud -> part[blockIdx.x]; all TB threads call
+__device__ inline void center_scan(const double *cloud, long long n, int d, int R, double *part, double *smem) {
+    const double *w = cloud + (long long)(R - 1) * n;
+    const double inf = __builtin_inf();
+    long long beg, end;
+    block_chunk(n, gridDim.x, blockIdx.x, beg, end);
+    for (int a = 0; a < d; ++a) {
+        const double *x = cloud + (long long)a * n;
+        double nlo = -inf, hi = -inf;
+        for (long long i = beg + threadIdx.x; i < end; i += TB) {
+            const double v = x[i];
+            if (w[i] > 0.0 && fabs(v) < inf) { nlo = fmax(nlo, -v); hi = fmax(hi, v); }
+        }
+        nlo = block_max(nlo, smem, TB / 64);
+        hi = block_max(hi, smem, TB / 64);
+        if (threadIdx.x == 0) { part[((long long)blockIdx.x * d + a) * 2] = nlo; part[((long long)blockIdx.x * d + a) * 2 + 1] = hi; }
+    }
+}
+// a column's shift from its (-min, max): the midrange unless 0 is within a quarter of the range of it (no live particle: NaN, shift 0)
+__device__ inline double center_rule(double nlo, double hi) {
+    const double lo = -nlo, mid = 0.5 * lo + 0.5 * hi, range = hi - lo;
+    return (fabs(mid) < __builtin_inf() && fabs(mid) > 0.25 * range) ? mid : 0.0;
+}
+static __global__ void __launch_bounds__(TB) k_center_probe(const double *cloud, long long n, int d, int R, double *part) {
+    __shared__ double smem[TB / 64];
+    center_scan(cloud, n, d, R, part, smem);
+}
+// block rows -> this shard's row of 2 d maxima and, behind them, whether its cloud came from outside (a sum all-reduce of rows in which
+// every shard fills only its own is a gather)
+static __global__ void __launch_bounds__(192) k_center_row(const double *part, int nb, int d, double *row, double stale) {
+    const int t = threadIdx.x;
+    if (t < 2 * d) {
+        double m = -__builtin_inf();
+        for (int b = 0; b < nb; ++b) m = fmax(m, part[(long long)b * 2 * d + t]);
+        row[t] = m;
+    } else if (t == 2 * d) row[t] = stale;
+}
+// the shards' rows -> out[0 .. d) the shift, out[d] whether to take it (a fresh chain, or some shard's cloud came from outside)
+static __global__ void __launch_bounds__(128) k_center_shift(const double *rows, int world, int d, int fresh, double *out) {
+    const int a = threadIdx.x, ld = 2 * d + 1;
+    if (a < d) {
+        double nlo = -__builtin_inf(), hi = -__builtin_inf();
+        for (int r = 0; r < world; ++r) { nlo = fmax(nlo, rows[(long long)r * ld + 2 * a]); hi = fmax(hi, rows[(long long)r * ld + 2 * a + 1]); }
+        out[a] = center_rule(nlo, hi);
+    } else if (a == d) {
+        double s = 0.0;
+        for (int r = 0; r < world; ++r) s += rows[(long long)r * ld + 2 * d];
+        out[d] = (fresh || s > 0.0) ? 1.0 : 0.0;
+    }
+}
+static __global__ void __launch_bounds__(64) k_center_apply(DevState *st, const double *shift, int d) {
+    if (shift[d] != 0.0 && (int)threadIdx.x < d) st->shift[threadIdx.x] = shift[threadIdx.x];
+}
+// One handle on its own: probe, rows -> shift and the store into DevState in ONE launch - the block that draws the last ticket finishes
+// (same maxima, same shift as the four launches of a group).  *ticket is 0 before the launch and 0 again after it.
+static __global__ void __launch_bounds__(TB) k_center_one(const double *cloud, long long n, int d, int R, double *part, int *ticket, DevState *st) {
+    __shared__ double smem[TB / 64];
+    __shared__ int s_last;
+    center_scan(cloud, n, d, R, part, smem);
+    if (threadIdx.x == 0) {
+        __threadfence();                                   // this block's row before its ticket
+        s_last = atomicAdd(ticket, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    const volatile double *vp = part;                      // the other blocks' rows: written during this launch
+    const double inf = __builtin_inf();
+    for (int a = 0; a < d; ++a) {                          // (one row per thread and trip: a thread walking all rows waits out a memory round trip per row)
+        double nlo = -inf, hi = -inf;
+        for (int b = threadIdx.x; b < (int)gridDim.x; b += TB) { nlo = fmax(nlo, vp[((long long)b * d + a) * 2]); hi = fmax(hi, vp[((long long)b * d + a) * 2 + 1]); }
+        nlo = block_max(nlo, smem, TB / 64);
+        hi = block_max(hi, smem, TB / 64);
+        if (threadIdx.x == 0) st->shift[a] = center_rule(nlo, hi);
+    }
+    if (threadIdx.x == 0) *ticket = 0;
+}
 #endif
 
 // generic fixed-order reduction of block partials into out[0..m) (1 block)

@@ -139,6 +139,7 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
     }
     const int base = cont ? s.stage - 1 : 0;                // stages completed before this call
     if (push_state(h)) return SMCMI_ERR_HIP;
+    if (int e = center_single(h, !cont)) return e;           // the chain's first moments are centred on the cloud (kernels.hpp k_center_probe)
     // the arrival counters of the two-level totals (PrepRed) start every run at zero: a launch whose wait timed out (SMCMI_ERR_TIMEOUT,
     // the run is void) may have left late arrivals behind - in stream order they precede this fill
     HIP_TRY(hipMemsetAsync(h->d_prep_tick, 0, 8 * sizeof(double), h->stream));

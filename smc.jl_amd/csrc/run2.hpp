@@ -281,6 +281,10 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     // start; =<k >= 3> (development): stage k's lagged shift is made to overflow, =<-k>: to underflow.
     static const int lag_env = getenv("SMCMI_SHIFT_LAG") ? atoi(getenv("SMCMI_SHIFT_LAG")) : 1;
     bool shift_lag = !adaptive && lag_env != 0;
+    // the shift of the chain's first moments (kernels.hpp k_center_probe): taken from the cloud before the set-up below, applied behind each push
+    if (g.world > MAX_SHARDS) return set_err(SMCMI_ERR_ARG, "too many shards");
+    const bool alone = g.world == 1 && g.hs.size() == 1;            // (one handle: center_single behind its push, below)
+    if (!alone) { if (int e = center_group(g, !cont)) return e; }
     // ---- per-handle set-up: run parameters and the stage-1 state in DevState (as engine 1), then imported into Ctl2
     for (auto *h : g.hs) {
         HIP_TRY(hipSetDevice(h->cfg.device));
@@ -318,6 +322,8 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             s.ess_prev = rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts;
         }
         if (push_state(h)) return SMCMI_ERR_HIP;
+        if (alone) { if (int e = center_single(h, !cont)) return e; }
+        else center_apply(h);
         if (!cont) {
             HIP_TRY(hipMemsetAsync(h->rec.resampled, 0, sizeof(int) * h->cfg.max_stages, h->stream));
             if (h->cfg.store_history) {

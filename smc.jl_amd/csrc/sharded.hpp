@@ -331,6 +331,48 @@ static int ensure_shard_buffers(smcmi_handle *h) {
     return 0;
 }
 
+
+// The shift of a chain's first moments over all shards (smcmi.hip center_probe): every shard's row of column minima / maxima, gathered by the
+// sum all-reduce, the same shift on every shard.  The shards' "my cloud came from outside" words travel with the rows, so every rank takes
+// the same decision on a continuation without knowing the others' history; the caller enqueues center_apply behind the push of each
+// handle's DevState.
+static_assert(MAX_SHARDS <= CENTER_SLOTS, "one centre row per shard");
+static int center_group(ShardGroup &g, bool fresh) {
+    if (!center_on()) return 0;
+    const int d = g.hs[0]->d;
+    if (!fresh) {
+        // a continuation: the shards' "my cloud came from outside" words first - in-process shards are all here; ranks sum theirs - and
+        // nothing more when no cloud did (stage-at-a-time drivers continue once per stage)
+        bool any = false;
+        for (auto *h : g.hs) any = any || h->center_stale;
+        if (g.rccl) {
+            static const double word[2] = {0.0, 1.0};
+            smcmi_handle *h = g.hs[0];
+            HIP_TRY(hipSetDevice(h->cfg.device));
+            HIP_TRY(hipMemcpyAsync(center_rows(h), &word[any ? 1 : 0], sizeof(double), hipMemcpyHostToDevice, h->stream));
+            if (int rc2 = g.allreduce([](smcmi_handle *q) { return center_rows(q); }, 1)) return rc2;
+            double sum = 0.0;
+            HIP_TRY(hipMemcpyAsync(&sum, center_rows(h), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            any = sum > 0.0;
+        }
+        if (!any) {                              // center_apply's word: nothing to take
+            for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); HIP_TRY(hipMemsetAsync(center_out(h) + d, 0, sizeof(double), h->stream)); }
+            return 0;
+        }
+        // (the clouds came through smcmi_upload_cloud and its kin, which pull the state: h_st.cur below is the device's)
+    }
+    for (auto *h : g.hs) {
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        const int rank = g.world > 1 ? (g.rccl ? h->rank : shard_rank(h)) : 0;
+        if (int e = center_probe(h, rank, g.world)) return e;
+    }
+    const int count = g.world * (2 * d + 1);
+    if (g.world > 1) { if (int rc2 = g.allreduce([](smcmi_handle *h) { return center_rows(h); }, count)) return rc2; }
+    for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); center_shift(h, g.world, fresh); }
+    return 0;
+}
+
 // one stage, phase by phase over all local shards (the phases between collectives are independent per shard)
 static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *res) {
     smcmi_handle *h0 = g.hs[0];
@@ -400,6 +442,9 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             HIP_TRY(hipMemcpyAsync(h->d_hist_W, h->cl.buf[0] + (long long)(h->R - 1) * h->n, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
         }
     }
+    if (g.world > MAX_SHARDS) return set_err(SMCMI_ERR_ARG, "too many shards");
+    if (int e = center_group(g, !rc->continue_run)) return e;
+    for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); center_apply(h); }
     // stage 1's energy shift: largest energy of the initial cloud over all shards (slots after the ES row: a sum all-reduce
     // in which every shard fills only its own slot is a gather)
     if (g.world > MAX_SHARDS) return set_err(SMCMI_ERR_ARG, "too many shards");

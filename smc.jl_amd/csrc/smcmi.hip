@@ -44,6 +44,42 @@ static int forget_e_seen(smcmi_handle *h) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
+
+// ---- the shift of the one-pass moments at the head of a chain (kernels.hpp k_center_probe): all in stream order, no host round trip.
+// center_probe leaves this shard's row (rank `rank` of `world`) in d_center - the other rows zero, for the gather-by-sum of a group;
+// center_shift turns the gathered rows into the shift; center_apply, enqueued behind the push of the chain's first DevState, puts it there.
+// SMCMI_CENTER=0 (development): the shift stays what the handle holds - 0 at the head of a run, the last mean it computed otherwise - the
+// arithmetic before the centre was taken from the cloud (tests/test_gpu_moment_range.py records its errors)
+static bool center_on() { static const int on = getenv("SMCMI_CENTER") ? atoi(getenv("SMCMI_CENTER")) : 1; return on != 0; }
+static inline double *center_rows(smcmi_handle *h) { return h->d_center; }
+static inline double *center_out(smcmi_handle *h) { return h->d_center + (size_t)CENTER_SLOTS * (2 * h->d + 1); }
+static int center_probe(smcmi_handle *h, int rank, int world) {
+    const int d = h->d, ld = 2 * d + 1;
+    if (rank < 0 || rank >= world || world > CENTER_SLOTS) return set_err(SMCMI_ERR_ARG, "too many shards");
+    if (!center_on()) return 0;
+    double *part = center_out(h) + d + 1;
+    if (world > 1) HIP_TRY(hipMemsetAsync(center_rows(h), 0, sizeof(double) * (size_t)world * ld, h->stream));
+    k_center_probe<<<h->nb_c, TB, 0, h->stream>>>(h->cl.buf[h->h_st.cur], h->n, d, h->R, part);
+    k_center_row<<<1, 192, 0, h->stream>>>(part, h->nb_c, d, center_rows(h) + (size_t)rank * ld, h->center_stale ? 1.0 : 0.0);
+    return 0;
+}
+static void center_shift(smcmi_handle *h, int world, bool fresh) {
+    if (!center_on()) return;
+    k_center_shift<<<1, 128, 0, h->stream>>>(center_rows(h), world, h->d, fresh ? 1 : 0, center_out(h));
+}
+static void center_apply(smcmi_handle *h) {
+    if (!center_on()) return;
+    k_center_apply<<<1, 64, 0, h->stream>>>(h->d_st, center_out(h), h->d);
+    h->center_stale = false;
+}
+// one handle on its own (every single-handle run, the stand-alone smcmi_moments): ONE launch behind the push of its DevState, nothing the host waits for
+static int center_single(smcmi_handle *h, bool fresh) {
+    if ((!fresh && !h->center_stale) || !center_on()) return 0;
+    double *part = center_out(h) + h->d + 1;
+    k_center_one<<<h->nb_c, TB, 0, h->stream>>>(h->cl.buf[h->h_st.cur], h->n, h->d, h->R, part, reinterpret_cast<int *>(part + (size_t)2 * h->d * h->nb_c), h->d_st);
+    h->center_stale = false;
+    return 0;
+}
 // The stand-alone calls (smcmi_correct, smcmi_ess_at, smcmi_solve_phi) are no part of a stage chain and have no energy maximum at hand: one
 // k_energy_max launch takes the cloud's - of the generalised energy of h->h_st.rp.pw / logp_old (kernels.hpp energy_base) - and the call shifts
 // by it like a stage does, so that it holds the reference's range (and more) instead of half of it.  Pushes h->h_st as the caller has set it
@@ -180,6 +216,7 @@ extern "C" int smcmi_create(const smcmi_config *cfg, smcmi_handle **out) {
         return SMCMI_ERR_HIP;
     h->nb_e = (int)std::min<long long>(512, std::max<long long>(1, (n + 511) / 512));      // (512 rows, not 1024: less for the prepare launch to total - measured 2-4 % per run from 4e5 to 1e7 particles)
     h->nb_m = (int)std::min<long long>(256, std::max<long long>(1, (n + MT - 1) / MT));
+    h->nb_c = (int)std::min<long long>(256, std::max<long long>(1, (n + 1023) / 1024));
     h->nb_mr = (int)std::min<long long>(512, std::max<long long>(std::min<long long>(64, (n + TB - 1) / TB), n / 1024));
     // mutation block size: largest of 256/128/64 threads whose per-thread LDS vectors fit 64 KiB
     for (int T : {256, 128, 64}) {
@@ -201,9 +238,11 @@ extern "C" int smcmi_create(const smcmi_config *cfg, smcmi_handle **out) {
         dmalloc(&h->d_chunk_off, h->nb_e) || dmalloc(&h->d_cum, n) || dmalloc(&h->d_anc, n) ||
         dmalloc(&h->d_part_mom, (size_t)std::max(h->nb_m, h->nb_mr) * h->npairs) || dmalloc(&h->d_totals, h->npairs) ||
         dmalloc(&h->d_acc_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(&h->d_esum_part, (size_t)std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4}) * ES) || dmalloc(&h->d_esum_red, (size_t)ESUM_RED_ROWS * (ES + 1)) || dmalloc(&h->d_emax_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(&h->d_comm, h->comm_cap) || dmalloc(&h->d_offsets, n) ||
+        dmalloc(&h->d_center, (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * h->nb_c + 1)) ||
         dmalloc(&h->d_flag, 4) || dmalloc(&h->d_mix, (size_t)10 * (3 * 100 + 22)) || dmalloc(&h->d_mixpos, 100))
         return SMCMI_ERR_HIP;
     h->d_prep_tick = reinterpret_cast<int *>(h->d_prep_rows + (size_t)PREP_G * PT);
+    HIP_TRY(hipMemset(h->d_center + (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * h->nb_c), 0, sizeof(double)));      // k_center_one's ticket
     HIP_TRY(hipMemset(h->d_prep_tick, 0, 8 * sizeof(double)));
     if (h->cfg.store_history) {
         if (dmalloc(&h->d_hist_w, (size_t)n * ms) || dmalloc(&h->d_hist_W, (size_t)n * ms)) return SMCMI_ERR_HIP;
@@ -250,7 +289,7 @@ extern "C" int smcmi_destroy(smcmi_handle *h) {
                     h->d_part_fin, h->d_part_cm, h->d_prep_rows, h->d_wt, h->d_chunk_off, h->d_cum, h->d_anc, h->d_part_mom, h->d_totals, h->d_acc_part, h->d_esum_part, h->d_esum_red, h->d_emax_part, h->d_zbuf,
                     h->d_comm, h->d_offsets, h->d_hist_w, h->d_hist_W, h->d_prop, h->d_prop_lp, h->d_prop_q,
                     h->d_lik_new, h->d_lik_old, h->d_acc_count, h->d_flag, h->d_cum_full, h->d_part_full, h->d_off_full,
-                    h->d_tot_ess, h->d_tot_fin, h->d_tot_mom, h->d_tot_acc, h->d_full_w, h->d_full_cloud, h->d_prof, h->d_mix, h->d_mixpos, h->d_snap};
+                    h->d_tot_ess, h->d_tot_fin, h->d_tot_mom, h->d_tot_acc, h->d_full_w, h->d_full_cloud, h->d_prof, h->d_mix, h->d_mixpos, h->d_snap, h->d_center};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -367,6 +406,7 @@ extern "C" int smcmi_upload_cloud(smcmi_handle *h, const double *particles) {
     if (!h || !particles) return set_err(SMCMI_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (pull_state(h) || forget_e_seen(h)) return SMCMI_ERR_HIP;
+    h->center_stale = true;
     HIP_TRY(hipMemcpy(h->cl.buf[h->h_st.cur], particles, sizeof(double) * h->n * h->R, hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());          // (null-stream copy: not ordered with the handle's non-blocking stream)
     return 0;
@@ -375,6 +415,7 @@ extern "C" int smcmi_upload_cloud_device(smcmi_handle *h, const double *dev_part
     if (!h || !dev_particles) return set_err(SMCMI_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (pull_state(h) || forget_e_seen(h)) return SMCMI_ERR_HIP;
+    h->center_stale = true;
     // (the caller's pointer may be peer-device memory without peer access, or a misaligned view: the runtime's copy handles both)
     HIP_TRY(hipMemcpyAsync(h->cl.buf[h->h_st.cur], dev_particles, sizeof(double) * (size_t)h->n * h->R, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -393,6 +434,7 @@ extern "C" int smcmi_cloud_device_ptr(smcmi_handle *h, double **dev_ptr, int64_t
     if (pull_state(h)) return SMCMI_ERR_HIP;
     *dev_ptr = h->cl.buf[h->h_st.cur];
     if (ld) *ld = h->n;
+    h->center_stale = true;                    // (the pointer is writable: what the caller does to the cloud through it is a cloud from outside)
     return 0;
 }
 extern "C" int smcmi_sync(smcmi_handle *h) {
@@ -418,6 +460,7 @@ static int need_model(smcmi_handle *h, int lik) {
 static int callback_init_from_prior(smcmi_handle *h);
 extern "C" int smcmi_init_from_prior(smcmi_handle *h) {
     if (int rc = need_model(h, 2)) return rc;
+    h->center_stale = true;
     if (closure_lik(h)) return callback_init_from_prior(h);           // user likelihood: device draws, the callback scores
     if (h->d > 64) return set_err(SMCMI_ERR_UNSUPPORTED, "device prior sampling: the RNG tags carry the parameter index in 6 bits");
     HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
@@ -631,6 +674,7 @@ extern "C" int smcmi_bridge_resample(smcmi_handle *dst, smcmi_handle *src, int32
     if (n_out == 0) return 0;
     HIP_TRY(hipSetDevice(src->cfg.device));
     if (pull_state(src) || pull_state(dst)) return SMCMI_ERR_HIP;
+    dst->center_stale = true;
     double *d_off = nullptr;
     if (offsets) {
         const long long cnt = method == SMCMI_RESAMPLE_MULTINOMIAL ? n_out : 1;
@@ -661,6 +705,7 @@ extern "C" int smcmi_copy_rows(smcmi_handle *dst, int64_t dst_row0, smcmi_handle
     if (n_rows == 0) return 0;
     HIP_TRY(hipSetDevice(src->cfg.device));
     if (pull_state(src) || pull_state(dst)) return SMCMI_ERR_HIP;
+    dst->center_stale = true;
     HIP_TRY(hipMemcpy2DAsync(dst->cl.buf[dst->h_st.cur] + dst_row0, sizeof(double) * dst->n, src->cl.buf[src->h_st.cur] + src_row0,
                              sizeof(double) * src->n, sizeof(double) * n_rows, (size_t)src->R, hipMemcpyDeviceToDevice, src->stream));
     HIP_TRY(hipStreamSynchronize(src->stream));
@@ -739,12 +784,23 @@ extern "C" int smcmi_moments(smcmi_handle *h, double *mean, double *cov) {
     if (!h || !mean || !cov) return set_err(SMCMI_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->cfg.device));
     const int d = h->d;
+    if (int e = center_single(h, false)) return e;      // the first moments of a cloud from outside: centred on the cloud, not on what the handle saw before
     const int nbm = launch_moments(h, nullptr, 1);
     k_moments_reduce<<<(h->npairs + 63) / 64, 1024, 0, h->stream>>>(h->d_st, h->d_part_mom, nbm, h->npairs, h->d_totals, 1);
     k_finalize_moments<<<1, 64, 0, h->stream>>>(h->d_st, h->d_totals, d);
     if (pull_state(h)) return SMCMI_ERR_HIP;
     for (int a = 0; a < d; ++a) mean[a] = h->h_st.mean[a];
     for (int e = 0; e < d * d; ++e) cov[e] = h->h_st.cov[e];
+    return 0;
+}
+
+// parity aid: θ̄ and R as the last stage (any engine) or the last smcmi_moments left them in DevState - a copy, nothing is launched
+extern "C" int smcmi_debug_stage_moments(smcmi_handle *h, double *mean, double *cov) {
+    if (!h || !mean || !cov) return set_err(SMCMI_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (pull_state(h)) return SMCMI_ERR_HIP;
+    for (int a = 0; a < h->d; ++a) mean[a] = h->h_st.mean[a];
+    for (int e = 0; e < h->d * h->d; ++e) cov[e] = h->h_st.cov[e];
     return 0;
 }
 
@@ -1205,6 +1261,8 @@ static int run2_guarded(ShardGroup &g, const smcmi_run_config *rc, smcmi_result 
             HIP_TRY(hipMemcpyAsync(h->d_snap + cloud_n, h->d_st, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream));
         }
     }
+    std::vector<bool> stale;                  // (a repeat starts from the snapshot: its shift is the one from before this call)
+    for (auto *h : g.hs) stale.push_back(h->center_stale);
     int e = run2_impl(g, rc, res);
     if (e == SMCMI_ERR_TIMEOUT && may_seg && h0->e2 && h0->e2->e3_state < 0) {
         if (getenv("SMCMI_TRACE")) fprintf(stderr, "[smcmi3] segment time-out: the run is repeated as launches from the cloud it started with\n");
@@ -1216,6 +1274,7 @@ static int run2_guarded(ShardGroup &g, const smcmi_run_config *rc, smcmi_result 
             HIP_TRY(hipStreamSynchronize(h->stream));
             h->seg_timeouts += 1;
         }
+        for (size_t q = 0; q < g.hs.size(); ++q) g.hs[q]->center_stale = stale[q];
         e = run2_impl(g, rc, res);
     }
     return e;

@@ -111,6 +111,7 @@ SYMBOLS = [
     ("smcmi_correct", C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(StageStats)]),
     ("smcmi_resample", C.c_int, [_H, C.c_int32, C.c_uint32, dp, lp]),
     ("smcmi_moments", C.c_int, [_H, dp, dp]),
+    ("smcmi_debug_stage_moments", C.c_int, [_H, dp, dp]),
     ("smcmi_mutate", C.c_int, [_H, dp, dp, ip, ip, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_uint32, dp]),
     ("smcmi_propose", C.c_int, [_H, dp, dp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_uint32, dp, dp, dp]),
     ("smcmi_accept", C.c_int, [_H, dp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32]),

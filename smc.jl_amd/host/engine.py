@@ -228,6 +228,12 @@ class Engine:
         check(self._L.smcmi_moments(self._h, _d(mean), _d(cov)))
         return mean, cov
 
+    def stage_moments(self):
+        """(θ̄, R) the last stage used for its proposals, as the engine left them (smcmi_debug_stage_moments): nothing is recomputed."""
+        mean, cov = np.empty(self.d), np.empty((self.d, self.d))
+        check(self._L.smcmi_debug_stage_moments(self._h, _d(mean), _d(cov)))
+        return mean, cov
+
     def mutate(self, mu_free, Sigma_free, block_ptr, blocks_free, phi_n, phi_prev, c, alpha, n_mh_steps, stage):
         mu, S = _f64(mu_free), _f64(Sigma_free)
         bp, bf = np.ascontiguousarray(block_ptr, dtype=np.int32), np.ascontiguousarray(blocks_free, dtype=np.int32)

@@ -323,6 +323,12 @@ function stage_records(h::Handle)
                 h, phi, ess, cs, acc, rs))
     return phi, ess, cs, acc, rs
 end
+# parity aid: (θ̄, R) the last stage used for its proposals, as the engine left them (row-major on the C side; R before (R + R') / 2)
+function stage_moments(h::Handle, d::Integer)
+    m = Vector{Float64}(undef, d); R = Matrix{Float64}(undef, d, d)
+    check(ccall((:smcmi_debug_stage_moments, LIB), Cint, (Handle, Ptr{Float64}, Ptr{Float64}), h, m, R))
+    return m, permutedims(R)
+end
 function print_stages(h::Handle, cloud::Cloud, parameters, regime_switching::Bool; verbose::Symbol = :low, use_fixed_schedule::Bool = true)
     VERBOSITY[verbose] >= VERBOSITY[:low] || return
     phi, ess, cs, acc, rs = stage_records(h)

@@ -210,8 +210,9 @@ def test_moments_vs_oracle(orc, n, d):
     mean, cov = e.moments()
     np.testing.assert_allclose(mean, orc.weighted_mean(P), rtol=1e-12)
     C = orc.weighted_cov(P)
-    np.testing.assert_allclose(cov, C, rtol=1e-8, atol=1e-9 * np.abs(C).max())
-    # a second call re-centres on the first mean: agreement tightens to rounding
+    # (the first call on an uploaded cloud is centred on the cloud itself - kernels.hpp k_center_probe - and is as good as the second,
+    # which is centred on the first mean; tests/test_gpu_moment_range.py takes both to the reference's rounding)
+    np.testing.assert_allclose(cov, C, rtol=1e-10, atol=1e-12 * np.abs(C).max())
     mean2, cov2 = e.moments()
     np.testing.assert_allclose(cov2, C, rtol=1e-10, atol=1e-12 * np.abs(C).max())
     np.testing.assert_allclose(mean2, mean, rtol=1e-13)
