@@ -75,8 +75,7 @@ static int ensure_callback_buffers(smcmi_handle *h) {
 // costs an event wait and an invocation of the user's function: ~20 µs); SMCMI_CB_CHUNKS=<k> (1 = the whole batch at once: the documented
 // opt-out for callbacks with per-batch state, include/smcmi.h, and the phase profile's serial reference)
 static int callback_chunks(long long n) {
-    static const int forced = getenv("SMCMI_CB_CHUNKS") ? atoi(getenv("SMCMI_CB_CHUNKS")) : 0;
-    if (forced > 0) return std::min(forced, CB_MAX_CHUNKS);
+    if (sw().cb_chunks > 0) return std::min(sw().cb_chunks, CB_MAX_CHUNKS);
     return (int)std::max<long long>(1, std::min<long long>(8, n / 12288));
 }
 static inline double cb_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -265,67 +264,24 @@ static int callback_init_from_prior(smcmi_handle *h) {
 // The whole loop with host likelihoods: engine 1's full stage (src/smc_main.jl:377-508 in its kernel sequence) up to the proposal
 // set-up, the callback mutation, one host sync per stage (the callback needs the proposals on the host anyway).
 static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res) {
-    const int nf = h->h_model.n_free;
-    if (rc->n_blocks < 1 || rc->n_blocks > nf || ((nf + rc->n_blocks - 1) / rc->n_blocks) * (rc->n_blocks - 1) >= nf)
-        return set_err(SMCMI_ERR_ARG, "n_blocks incompatible with the number of free parameters");
-    if (rc->n_phi < 2 || rc->n_mh_steps < 1) return set_err(SMCMI_ERR_ARG, "bad n_phi / n_mh_steps");
-    if (rc->resampling_method != SMCMI_RESAMPLE_SYSTEMATIC && rc->resampling_method != SMCMI_RESAMPLE_MULTINOMIAL)
-        return set_err(SMCMI_ERR_ARG, "Invalid resampler in SMC. Options are systematic or multinomial");
+    if (int e = check_run_config(h, rc)) return e;
     const bool adaptive = !rc->use_fixed_schedule;
     const bool tempered = closure_lik(h, 1);
     const bool on_device = h->dcb[0] != nullptr;          // the likelihood is a device function (devcallback.hpp): no staging buffers, no copy streams
-    if (!adaptive && rc->n_phi > h->cfg.max_stages) return set_err(SMCMI_ERR_CAPACITY, "max_stages < n_phi");
     if (int e = on_device ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e;
     if (pull_state(h)) return SMCMI_ERR_HIP;
-    std::vector<double> sched(rc->n_phi);
-    for (int k = 0; k < rc->n_phi; ++k) sched[k] = pow((double)k / (double)(rc->n_phi - 1), rc->lambda);
+    const std::vector<double> sched = make_schedule(rc);
     if (upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
     DevState &s = h->h_st;
-    RunParams rp{};
-    rp.n_parts = h->cfg.n_parts; rp.n_blocks = rc->n_blocks; rp.n_mh_steps = rc->n_mh_steps; rp.n_phi = rc->n_phi;
-    rp.resampling_method = rc->resampling_method; rp.use_fixed_schedule = rc->use_fixed_schedule;
-    rp.threshold = rc->threshold_ratio * (double)h->cfg.n_parts;
-    rp.alpha = rc->alpha; rp.target = rc->target; rp.tempering_target = rc->tempering_target;
-    rp.pw = rc->tempered_update_prior_weight; rp.logp_old = rc->log_prob_old_data;
-    rp.max_stages = h->cfg.max_stages; rp.store_history = h->cfg.store_history;
-    rp.stall_on_exhaust = 1;
-    rp.phi_rtol = rc->phi_rtol > 0.0 ? rc->phi_rtol : (rc->phi_rtol < 0.0 ? 0.0 : DEFAULT_PHI_RTOL);
-    rp.stop_stage = rc->stop_after_stage > 0 ? rc->stop_after_stage : 0;
     const bool cont = rc->continue_run != 0;
-    if (cont) {
-        if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
-        if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");
-        s.rp = rp; s.done = 0; s.err = 0; s.skip_fold = 1; s.do_resample = 0;
-        s.e_seen = __builtin_nan("");                           // (as run1.hpp: this path keeps no Begin2::e_seen)
-    } else {
-        const int cur = s.cur;
-        memset(&s, 0, sizeof(DevState));
-        s.e_seen = __builtin_nan("");
-        s.rp = rp; s.cur = cur;
-        s.stage = 1; s.j = 2;
-        s.c = rc->c; s.accept = rc->target;
-        s.ess_prev = rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts;
-    }
+    if (int e = start_state(h, rc, make_run_params(h, rc), false)) return e;
     const int base = cont ? s.stage - 1 : 0;
-    if (push_state(h)) return SMCMI_ERR_HIP;
     if (int e = center_single(h, !cont)) return e;
-    if (!cont) {
-        const double v0[4] = {0.0, rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts, rc->c, rc->target};
-        HIP_TRY(hipMemcpyAsync(h->rec.phi, &v0[0], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->rec.ess, &v0[1], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->rec.c, &v0[2], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->rec.accept, &v0[3], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemsetAsync(h->rec.resampled, 0, sizeof(int) * h->cfg.max_stages, h->stream));
-        if (h->cfg.store_history) {
-            HIP_TRY(hipMemsetAsync(h->d_hist_w, 0, sizeof(double) * h->n, h->stream));
-            HIP_TRY(hipMemcpyAsync(h->d_hist_W, h->cl.buf[0] + (long long)(h->R - 1) * h->n, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
+    if (!cont) { if (int e = first_records(h, rc)) return e; }
     h->rng_ahead = false;
     // adaptive schedules: the accept launches leave the energy power sums the phi predictor reads, so a stage's certificate search starts
     // from rings around the predicted root - one pass instead of six - and the energy maxima the shifted weights need
-    h->cb_energy = adaptive && !getenv("SMCMI_NO_PREDICTOR");
+    h->cb_energy = adaptive && !sw().no_predictor;
     const int acc_nb = h->nb_mut;                       // the split kernels are the generic (LDS) mutation kernels
     k_energy_max<<<acc_nb, TB, 0, h->stream>>>(h->cl, h->d_st, h->d_emax_part);
     const int first_passes = std::max(rc->solver_passes, FIRST_SOLVER_PASSES);
@@ -382,13 +338,8 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     if (pull_state(h)) return SMCMI_ERR_HIP;
     const auto t1 = std::chrono::steady_clock::now();
     res->kernel_ms_mutate = 0.0; res->n_mutate_launches = 0;
-    res->n_stages = s.stage; res->resamples = s.resamples; res->logmdd = s.logz; res->c = s.c; res->accept = s.accept;
-    res->seconds = std::chrono::duration<double>(t1 - t0).count();
-    res->solver_passes = s.solver_passes;
-    res->paused = (s.done == 5) ? 1 : 0;
+    finish_result(res, s, t0, t1);
     h->last_n_stages = s.stage;
     if (s.err == SMCMI_ERR_NAN_ESS) return nan_ess_error(h, h->cl.buf[0] + (long long)(h->R - 1) * h->n);
-    if (s.err) return err_from_state(s.err);
-    if (!s.done) return set_err(SMCMI_ERR_CAPACITY, "max_stages exceeded before the tempering schedule reached 1");
-    return 0;
+    return finish_error(s);
 }

@@ -6,8 +6,8 @@
 // ---- peer mailbox (stage2.hpp): allocation and the table of peer addresses
 // clear the sticky time-out flag and (re)load the time-out (SMCMI_MAILBOX_TIMEOUT_MS, default 10 s; read at every run)
 static int mbox_reset_flag(smcmi_handle *h, hipStream_t s) {
-    const char *ms = getenv("SMCMI_MAILBOX_TIMEOUT_MS");
-    const unsigned long long fl[MB_FLAG_WORDS] = {0ull, ms && atof(ms) > 0.0 ? (unsigned long long)(atof(ms) * 1e5) : (unsigned long long)MB_TIMEOUT_TICKS_DEFAULT};
+    const double ms = sw().per_run().mailbox_timeout_ms;
+    const unsigned long long fl[MB_FLAG_WORDS] = {0ull, ms > 0.0 ? (unsigned long long)(ms * 1e5) : (unsigned long long)MB_TIMEOUT_TICKS_DEFAULT};
     if (s) { HIP_TRY(hipMemcpyAsync(h->d_mbox + MB_WORDS, fl, sizeof(fl), hipMemcpyHostToDevice, s)); HIP_TRY(hipStreamSynchronize(s)); }
     else HIP_TRY(hipMemcpy(h->d_mbox + MB_WORDS, fl, sizeof(fl), hipMemcpyHostToDevice));
     return 0;

@@ -1,5 +1,6 @@
-// run1.hpp - engine 1's driver: the stage as a fixed kernel sequence (enqueue_stage) and smcmi_run, the entry point every one-handle run comes
-// through (it hands runs that qualify to engines 2 / 3: run2.hpp).  Included by smcmi.hip behind the stage primitives it enqueues.
+// run1.hpp - engine 1's driver: the stage as a fixed kernel sequence (enqueue_stage) and run1_impl, the run of one handle on it (smcmi_run,
+// the entry point every one-handle run comes through, is in smcmi.hip behind all drivers).  Included by smcmi.hip behind the stage primitives
+// it enqueues.
 #pragma once
 
 // ------------------------------------------------------------------------------------------------ whole loop
@@ -16,7 +17,6 @@ static void enqueue_stage(smcmi_handle *h, bool adaptive, int solver_passes, int
     hipStream_t s = h->stream;
     // spec: predict -> correct -> verify (kernels.hpp k_stage_begin): no certificate pass is enqueued at all - 4 launches
     const int P = (adaptive && !spec) ? p0 + solver_passes : 0;
-    static const int no_pred = getenv("SMCMI_NO_PREDICTOR") ? atoi(getenv("SMCMI_NO_PREDICTOR")) : 0;   // development only
     h->run_adaptive = adaptive;
     const int fin_slot = P == 0 ? 0 : (P & 1);
     // no selection expected and the register kernels apply: the correction pass gathers the moments too, k_prepare_mutation
@@ -29,7 +29,7 @@ static void enqueue_stage(smcmi_handle *h, bool adaptive, int solver_passes, int
         // (a host-callback mutation without cb_energy - sharded closure runs, fixed schedules - leaves neither energy sums nor energy maxima:
         // plain schedule walk, unshifted weights)
         const bool hm_plain = host_mut && !h->cb_energy;
-        const double *es = (adaptive && !no_pred && !hm_plain) ? h->d_esum_part : nullptr;
+        const double *es = (adaptive && !sw().no_predictor && !hm_plain) ? h->d_esum_part : nullptr;
         int es_nb = acc_nb, em_nb = acc_nb;
         const double *em = hm_plain ? nullptr : h->d_emax_part;
         // tens of thousands of rows are not for one block: blocks 1..ESUM_RED_ROWS of the same launch total a chunk each (k_stage_begin)
@@ -82,83 +82,24 @@ static int check_lik_pair(const smcmi_handle *h) {
         return set_err(SMCMI_ERR_STATE, "the new and the old likelihood must both be host callbacks or both device callbacks");
     return 0;
 }
-struct ShardGroup;
-static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res);
-static bool eng2_eligible(const smcmi_handle *h, int world, bool single, const smcmi_run_config *rc);
-static int run2_single(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res);
-
-extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res) {
-    if (int e = need_model(h, 2)) return e;
-    if (!rc || !res) return set_err(SMCMI_ERR_ARG, "null argument");
-    if (h->cfg.n_local != h->cfg.n_parts) return set_err(SMCMI_ERR_UNSUPPORTED, "smcmi_run drives a single shard; use the shard-level calls for multi-GPU");
-    res->n_segments = 0; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
-    res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
-    if (int e = check_lik_pair(h)) return e;
-    if (closure_lik(h)) return run_callback(h, rc, res);              // user likelihood: a host callback or a device callback (callback.hpp)
-    if (eng2_eligible(h, 1, true, rc)) return run2_single(h, rc, res);          // n_para <= 10: the two-launch stage (stage2.hpp)
-    const int nf = h->h_model.n_free;
-    if (rc->n_blocks < 1 || rc->n_blocks > nf || ((nf + rc->n_blocks - 1) / rc->n_blocks) * (rc->n_blocks - 1) >= nf)
-        return set_err(SMCMI_ERR_ARG, "n_blocks incompatible with the number of free parameters");
-    if (rc->n_phi < 2 || rc->n_mh_steps < 1) return set_err(SMCMI_ERR_ARG, "bad n_phi / n_mh_steps");
-    if (rc->resampling_method != SMCMI_RESAMPLE_SYSTEMATIC && rc->resampling_method != SMCMI_RESAMPLE_MULTINOMIAL)
-        return set_err(SMCMI_ERR_ARG, "Invalid resampler in SMC. Options are systematic or multinomial");
+// engine 1's run of one handle (smcmi_run sends it the runs that are neither closure runs nor engine 2's)
+static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res) {
+    if (int e = check_run_config(h, rc)) return e;
     const bool adaptive = !rc->use_fixed_schedule;
-    if (!adaptive && rc->n_phi > h->cfg.max_stages) return set_err(SMCMI_ERR_CAPACITY, "max_stages < n_phi");
     if (pull_state(h)) return SMCMI_ERR_HIP;
-    // proposed fixed schedule ((k-1)/(n_Φ-1))^λ, smc_main.jl:348-352
-    std::vector<double> sched(rc->n_phi);
-    for (int k = 0; k < rc->n_phi; ++k) sched[k] = pow((double)k / (double)(rc->n_phi - 1), rc->lambda);
+    const std::vector<double> sched = make_schedule(rc);
     if (upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
     DevState &s = h->h_st;
-    const int cur = s.cur;
-    RunParams rp{};
-    rp.n_parts = h->cfg.n_parts; rp.n_blocks = rc->n_blocks; rp.n_mh_steps = rc->n_mh_steps; rp.n_phi = rc->n_phi;
-    rp.resampling_method = rc->resampling_method; rp.use_fixed_schedule = rc->use_fixed_schedule;
-    rp.threshold = rc->threshold_ratio * (double)h->cfg.n_parts;
-    rp.alpha = rc->alpha; rp.target = rc->target; rp.tempering_target = rc->tempering_target;
-    rp.pw = rc->tempered_update_prior_weight; rp.logp_old = rc->log_prob_old_data;
-    rp.max_stages = h->cfg.max_stages; rp.store_history = h->cfg.store_history;
-    rp.stall_on_exhaust = 1;
-    rp.phi_rtol = rc->phi_rtol > 0.0 ? rc->phi_rtol : (rc->phi_rtol < 0.0 ? 0.0 : DEFAULT_PHI_RTOL);
-    rp.stop_stage = rc->stop_after_stage > 0 ? rc->stop_after_stage : 0;
-    // continue_run (continue_intermediate, smc_main.jl:334-335,355-361): keep the loop scalars, records and history the handle
-    // holds (left by a paused run, or put there by smcmi_set_loop_state / _set_stage_records / _set_history)
+    const RunParams rp = make_run_params(h, rc);
     const bool cont = rc->continue_run != 0;
-    if (cont) {
-        if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
-        if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");
-        s.rp = rp; s.done = 0; s.err = 0; s.skip_fold = 1; s.do_resample = 0;
-        s.e_seen = __builtin_nan("");                           // (engine 1 keeps no Begin2::e_seen: a later continuation on engines 2 / 3 takes the cloud's own maximum)
-    } else {
-        memset(&s, 0, sizeof(DevState));
-        s.e_seen = __builtin_nan("");
-        s.rp = rp; s.cur = cur;
-        s.stage = 1; s.j = 2;                                   // i = 1, j = 2 (smc_main.jl:198-199)
-        s.c = rc->c; s.accept = rc->target;                     // initialize_cloud_settings!, initialization.jl:196-211
-        s.ess_prev = rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts;   // tempered update: ESS of the old cloud (initialization.jl:199-200)
-    }
+    if (int e = start_state(h, rc, rp, false)) return e;
     const int base = cont ? s.stage - 1 : 0;                // stages completed before this call
-    if (push_state(h)) return SMCMI_ERR_HIP;
     if (int e = center_single(h, !cont)) return e;           // the chain's first moments are centred on the cloud (kernels.hpp k_center_probe)
     // the arrival counters of the two-level totals (PrepRed) start every run at zero: a launch whose wait timed out (SMCMI_ERR_TIMEOUT,
     // the run is void) may have left late arrivals behind - in stream order they precede this fill
     HIP_TRY(hipMemsetAsync(h->d_prep_tick, 0, 8 * sizeof(double), h->stream));
-    // stage-1 records and history columns (w[:,1] = 0, W[:,1] = weights; smc_main.jl:363-366)
-    if (!cont) {
-        const double v0[4] = {0.0, rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts, rc->c, rc->target};
-        HIP_TRY(hipMemcpyAsync(h->rec.phi, &v0[0], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->rec.ess, &v0[1], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->rec.c, &v0[2], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->rec.accept, &v0[3], sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemsetAsync(h->rec.resampled, 0, sizeof(int) * h->cfg.max_stages, h->stream));
-        if (h->cfg.store_history) {
-            HIP_TRY(hipMemsetAsync(h->d_hist_w, 0, sizeof(double) * h->n, h->stream));
-            HIP_TRY(hipMemcpyAsync(h->d_hist_W, h->cl.buf[cur] + (long long)(h->R - 1) * h->n, sizeof(double) * h->n,
-                                   hipMemcpyDeviceToDevice, h->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    if (getenv("SMCMI_PROF2") && !h->d_prof) { if (dmalloc(&h->d_prof, 32)) return SMCMI_ERR_HIP; }
+    if (!cont) { if (int e = first_records(h, rc)) return e; }
+    if (sw().prof2.set && !h->d_prof) { if (dmalloc(&h->d_prof, 32)) return SMCMI_ERR_HIP; }
     if (int e = ensure_zbuf(h, rc->n_mh_steps, rc->n_blocks)) return e;
     const int solver_passes = rc->solver_passes >= 1 ? rc->solver_passes : DEFAULT_SOLVER_PASSES;
     const int first_passes = std::max(solver_passes, FIRST_SOLVER_PASSES);
@@ -173,7 +114,7 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
     // resample), so the host enqueues the selection kernels only where it expects a resample; the device checks the expectation
     // (k_moments_reg) and stalls the run if it was wrong.  SMCMI_NO_SELECT_PREDICT=1 (development) keeps the full list everywhere,
     // =2 deliberately predicts "never" to exercise the stall path.
-    static const int sel_mode = getenv("SMCMI_NO_SELECT_PREDICT") ? atoi(getenv("SMCMI_NO_SELECT_PREDICT")) : 0;
+    const int sel_mode = sw().no_select_predict;
     // (Fixed schedules: extrapolating the ESS decay was tried and dropped - CAPM-like posteriors collapse within two or three
     // stages, 19 of 20 resamples stalled, and the per-batch sync it needs makes short stages host-bound.)
     const bool predict_select = adaptive && can_fuse_post(h) && sel_mode != 1;
@@ -184,9 +125,8 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
     // per batch makes short stages host-bound.  Instead the host stays `run_ahead` stages in front of the device WITHOUT a sync:
     // k_stage_begin posts its stage index and the stalling k_prepare_mutation a flag into host-mapped words (handle.hpp h_note)
     // which the enqueue loop polls; a drained stream (an error, a pause, phi = 1) also ends the wait.
-    static const int fixed_sel = getenv("SMCMI_FIXED_NO_SELECT") ? atoi(getenv("SMCMI_FIXED_NO_SELECT")) : 1;        // development: 0 = the seven-launch stage
     const int run_ahead = 1;      // (config 4: 30.6 ms at 1, 30.8 at 2, 31.1 at 4 - fewer idle launches behind a stall; measured in round 4, the switch retired in round 6)
-    bool fixed_ns = !adaptive && can_fuse_cm(h) && sel_mode != 1 && fixed_sel != 0;
+    bool fixed_ns = !adaptive && can_fuse_cm(h) && sel_mode != 1 && sw().fixed_no_select != 0;        // (development: SMCMI_FIXED_NO_SELECT=0 = the seven-launch stage)
     if (fixed_ns && !h->h_note) {
         void *hp = nullptr, *dp = nullptr;
         if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
@@ -202,9 +142,9 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
     if (fixed_ns) { h->h_note[0] = s.stage; h->h_note[1] = 0; }
     // (with a prior weight the correction's incremental weight differs from the solver's objective - quirk Q4 - so the ESS it
     // produces cannot verify a predicted root: those runs keep the certificate pass)
-    const bool spec_ok = predict_select && can_fuse_cm(h) && !getenv("SMCMI_NO_PREDICTOR") &&
+    const bool spec_ok = predict_select && can_fuse_cm(h) && !sw().no_predictor &&
                          rc->tempered_update_prior_weight == 0.0 && rp.phi_rtol > 0.0;
-    double pred_ess = cont ? s.ess_prev : (rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts);   // ESS after the last completed stage
+    double pred_ess = cont ? s.ess_prev : initial_ess(h, rc);   // ESS after the last completed stage
     int pred_rl = cont ? s.resampled_last : 0;                                             // resampled_last_period
     const auto t0 = std::chrono::steady_clock::now();
     int launched = 0, done = 0;
@@ -340,8 +280,7 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
             pred_ess = s.ess_prev;
             pred_rl = s.resampled_last;
         }
-        static const int trace = getenv("SMCMI_TRACE") ? atoi(getenv("SMCMI_TRACE")) : 0;   // development only
-        if (trace) {
+        if (sw().trace) {   // development only
             static long long last_passes = 0;
             if (pull_state(h)) return SMCMI_ERR_HIP;
             fprintf(stderr, "[smcmi] stage %d phi %.12e dphi %.6e pred %.6e relerr %.2e passes %lld ess %.1f rs %d\n", s.stage, s.phi_n,
@@ -369,42 +308,15 @@ extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resu
     if (pull_state(h)) return SMCMI_ERR_HIP;
     const auto t1 = std::chrono::steady_clock::now();
     res->kernel_ms_mutate = 0.0; res->n_mutate_launches = 0;
-    // An event pair brackets [previous kernel done -> this kernel done]: dispatch of the kernel included.  Calibrate that
-    // fixed part with pairs around an empty kernel and subtract it, so the figure is the kernel's own duration (what
-    // rocprofv3 --kernel-trace reports).
-    double ev_overhead_ms = 0.0;
-    if (profile && !evs.empty()) {
-        hipEvent_t c0, c1;
-        hipEventCreate(&c0); hipEventCreate(&c1);
-        const int reps = 64;
-        double acc_ms = 0.0;
-        int got = 0;
-        for (int r = 0; r < reps; ++r) {
-            k_fill<<<(unsigned)((h->n + 255) / 256), 256, 0, h->stream>>>(nullptr, 0, 0.0);      // (an empty launch of the mutation kernel's grid: event-overhead calibration)     // predecessor of comparable size
-            hipEventRecord(c0, h->stream);
-            k_fill<<<(unsigned)((h->n + 255) / 256), 256, 0, h->stream>>>(nullptr, 0, 0.0);      // (an empty launch of the mutation kernel's grid: event-overhead calibration)
-            hipEventRecord(c1, h->stream);
-            hipStreamSynchronize(h->stream);
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, c0, c1) == hipSuccess) { acc_ms += ms; ++got; }
-        }
-        hipEventDestroy(c0); hipEventDestroy(c1);
-        // an empty kernel of this grid itself lasts ~2.5 µs in a rocprofv3 kernel trace (wave launch + drain): leave that in
-        if (got) ev_overhead_ms = std::max(0.0, acc_ms / got - 0.0025);
-    }
+    const double ev_overhead_ms = (profile && !evs.empty()) ? event_overhead_ms(h) : 0.0;
     for (size_t k = 0; k + 1 < evs.size(); k += 2) {
         float ms = 0.f;
         if (ev_iter[k / 2] >= 0 && ev_iter[k / 2] < s.stage - 1 - base && hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) { res->kernel_ms_mutate += std::max(0.0, (double)ms - ev_overhead_ms); res->n_mutate_launches += 1; }
     }
     for (hipEvent_t e : evs) hipEventDestroy(e);
-    res->n_stages = s.stage; res->resamples = s.resamples; res->logmdd = s.logz; res->c = s.c; res->accept = s.accept;
-    res->seconds = std::chrono::duration<double>(t1 - t0).count();
-    res->solver_passes = s.solver_passes;
-    res->paused = (s.done == 5) ? 1 : 0;
+    finish_result(res, s, t0, t1);
     h->last_n_stages = s.stage;
     if (s.err == SMCMI_ERR_NAN_ESS) return nan_ess_error(h, h->spec_stage ? h->d_wt : h->cl.buf[0] + (long long)(h->R - 1) * h->n);
-    if (s.err) return err_from_state(s.err);
-    if (!s.done) return set_err(SMCMI_ERR_CAPACITY, "max_stages exceeded before the tempering schedule reached 1");
-    return 0;
+    return finish_error(s);
 }
 

@@ -25,105 +25,20 @@ static void free_eng2(Eng2 *e) {
     delete e;
 }
 
-// virtual-shard geometry of a handle that is shard `rank` of `world` (a function of N and the shard count's divisibility only)
-static bool make_geo2(const smcmi_handle *h, int world, int rank, bool single, Geo2 *out) {
-    Geo2 g{};
-    g.N = h->cfg.n_parts; g.n = h->n;
-    if (world < 1 || g.n * world != g.N) return false;
-    int V = 0;
-    for (int cand : {8, 4, 2, 1})
-        if (cand % world == 0 && g.n % (cand / world) == 0) { V = cand; break; }
-    if (!V) { if (world <= V2_MAXV) V = world; else return false; }
-    g.V = V; g.Vl = V / world; g.v0 = rank * g.Vl; g.nv = g.n / g.Vl;
-    if (g.nv < 1) return false;
-    // n_para > 10: the generic mutation body behind engine 2's prologues (stage2.hpp k2w_mutate) - 256 particles per block with one
-    // thread per particle, 64 with four lanes per particle (lgss_kalman on small clouds); rows always totalled per virtual shard (Tail2)
-    g.wide = h->d > 10 ? (use_ls4_mutate(h) ? 4 : 1) : 0;
-    if (g.wide) {
-        g.t2 = g.wide == 4 ? 64 : 256;
-        g.nb2 = (int)((g.nv + g.t2 - 1) / g.t2);
-        if (g.nv > 65536 || (long long)g.nb2 * g.Vl > 1024) return false;      // (a correction row is 512 particles, one per thread: nb1 <= 128)
-        g.direct = 0; g.inker = 1;
-        g.nb1 = (int)std::max<long long>(1, (g.nv + 511) / 512);
-        g.per1 = T1;
-        g.nbg = (int)std::max<long long>(1, std::min<long long>((g.nv + 511) / 512, 256));
-        g.perg = ((g.nv + g.nbg - 1) / g.nbg + 255) / 256 * 256;
-        *out = g;
-        return true;
-    }
-    g.t2 = 512;
-    g.nb2 = (int)((g.nv + g.t2 - 1) / g.t2);
-    // direct: every block totals the per-block rows itself - one handle, <= GRP rows per virtual shard, and the 512-thread mutation
-    // blocks (one per CU) resident at once
-    // (beyond 256 blocks - up to 62 per virtual shard - the persistent segments give every worker two chunks: stage3.hpp k3_segment<D, true, RIDE, 2>;
-    // eng2_eligible keeps such a cloud on engine 1 unless its run qualifies for them)
-    g.direct = (single && world == 1 && g.nb2 <= GRP && (long long)g.nb2 * V <= 2 * (256 - V2_MAXV)) ? 1 : 0;
-    if (getenv("SMCMI_E2_REDUCED")) g.direct = 0;                                    // development: force the k2_reduce path on one handle
-    // several handles with small shards: one 512-thread mutation block per CU as well, prologues in the kernels, fed by the gathered totals
-    g.inker = (g.direct || (!single && (long long)g.nb2 * g.Vl <= 256)) ? 1 : 0;
-    // large shards (stage2b.hpp k2b_mutate): the same 512-particle mutation blocks at half the registers - two per CU, 4 wavefronts per SIMD
-    // (256-thread blocks - 489 raw rows per virtual shard at 125 000 particles, paired into canonical rows by whoever totals them - cost
-    // the block that totals a shard's rows ~10 µs at the END of every mutation launch: twice the loads, a quarter of them in flight)
-    // correction blocks per virtual shard: 1024 particles per block (two passes of its 512 threads), at most 16 rows per virtual shard for
-    // K2's prologue to total while the cloud is small
-    // (the direct geometry: one correction row per 512 particles, the same particles as a mutation row - the persistent segment kernel
-    // of stage3.hpp holds one particle per thread and writes exactly these rows, so both engines total the same numbers)
-    // every geometry cuts a virtual shard the same way, so all of them total the same rows (<= 128 rows per virtual shard: the blocks
-    // grow beyond 512 particles for nv > 65 536, where the direct geometry does not exist)
-    g.nb1 = (int)std::max<long long>(1, g.direct ? g.nb2 : std::min<long long>((g.nv + 511) / 512, 128));
-    if (getenv("SMCMI_E2_NB1")) g.nb1 = std::max(1, std::min(atoi(getenv("SMCMI_E2_NB1")), g.direct ? 64 : 128));   // development only (tools/shard_rank_prof.sh: one rank's share of a larger run)
-    g.per1 = ((g.nv + g.nb1 - 1) / g.nb1 + T1 - 1) / T1 * T1;                        // whole passes of the block
-    // (one 512-slot tile per gather block up to GRP rows per virtual shard on one handle as on several: a cloud of 4 x odd or 2 x odd particles -
-    // 33 .. 64 rows per shard - had two-tile blocks on one handle until round 6, i.e. moment rows summed in another order than its sharded runs')
-    g.nbg = (int)std::max<long long>(1, std::min<long long>((g.nv + 511) / 512, g.direct ? GRP : 256));
-    g.perg = ((g.nv + g.nbg - 1) / g.nbg + 255) / 256 * 256;
-    // (a virtual shard of at most 256 particles: one gather block of ONE 512-slot tile all the same - the block a segment worker is, so that
-    // clouds of a few thousand particles resample inside their segments too)
-    if (g.direct && g.perg < 512) g.perg = 512;
-    if ((long long)g.V * g.nb1 > 1024) return false;
-    *out = g;
-    return true;
+// The plan (route.hpp) of handle h as shard `rank` of a run of `world` shards, `n_handles` of them in this process.  group_call: the run came
+// through smcmi_run_sharded / smcmi_run_group - it only picks the driver of a run engine 2 does not serve.
+static int handle_plan(const smcmi_handle *h, int world, int rank, int n_handles, bool rccl, bool group_call, const smcmi_run_config *rc, RunPlan *out) {
+    RunShape r = handle_shape(h);
+    r.world = world; r.rank = rank; r.n_handles = n_handles;
+    r.single = n_handles == 1 && !rccl; r.rccl = rccl; r.group_call = group_call;
+    int n_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->cfg.device));
+    *out = plan_run(r, rc->alpha, rc->n_blocks, rc->n_mh_steps, sw(), n_cu);
+    return 0;
 }
-// One handle whose particle count has no divisor among 8 / 4 / 2 that leaves it the direct geometry (100 001 particles: one virtual
-// shard of 196 rows - engine 1's stage at twice the time): virtual shards of ceil(n / V) particles, the last one shorter (vchunk and
-// k2_scan clamp at n; a block beyond the end holds no particle and publishes zero rows).  Only where no sharded run of the same
-// cloud shares the canonical order anyway (such a cloud runs on engine 1 today, which has another order).
-static bool make_geo2_uneven(const smcmi_handle *h, Geo2 *out) {
-    if (h->d > 10 || getenv("SMCMI_E2_REDUCED")) return false;
-    for (int V : {8, 4, 2}) {
-        Geo2 g{};
-        g.N = h->cfg.n_parts; g.n = h->n;
-        if (g.n != g.N) return false;
-        g.V = V; g.Vl = V; g.v0 = 0; g.nv = (g.n + V - 1) / V;
-        if ((long long)(V - 1) * g.nv >= g.n) continue;                              // (no empty virtual shard)
-        g.wide = 0; g.t2 = 512;
-        g.nb2 = (int)((g.nv + g.t2 - 1) / g.t2);
-        if (!(g.nb2 <= GRP && (long long)g.nb2 * V <= 2 * (256 - V2_MAXV))) continue;
-        g.direct = 1; g.inker = 1;
-        g.nb1 = g.nb2;
-        g.per1 = ((g.nv + g.nb1 - 1) / g.nb1 + T1 - 1) / T1 * T1;
-        g.nbg = (int)std::max<long long>(1, std::min<long long>((g.nv + 511) / 512, GRP));      // (one tile per gather block, like make_geo2's: in-place selection beyond 32 rows)
-        g.perg = ((g.nv + g.nbg - 1) / g.nbg + 255) / 256 * 256;
-        if (g.perg < 512) g.perg = 512;
-        *out = g;
-        return true;
-    }
-    return false;
-}
-
-// The geometry a handle gets (ensure_eng2 builds it, eng2_eligible asks whether engine 2 serves it: ONE rule for both).  `single`: a run of
-// smcmi_run on one handle - not a communicator of one rank, whose handle keeps the geometry its larger worlds have.  The uneven cut replaces
-// only a geometry that would send the handle to engine 1; a cloud forced onto engine 2 (SMCMI_ENGINE=2) keeps the canonical cut a sharded
-// run of the same cloud has, so the file's contract - results do not depend on the number of handles - holds for it.
-static bool handle_geo2(const smcmi_handle *h, int world, int rank, bool single, Geo2 *out) {
-    static const int eng = getenv("SMCMI_ENGINE") ? atoi(getenv("SMCMI_ENGINE")) : 0;
-    if (!make_geo2(h, world, rank, single, out)) return false;
-    if (single && world == 1 && !out->wide && !out->direct && eng != 2) { Geo2 gu; if (make_geo2_uneven(h, &gu)) *out = gu; }
-    return true;
-}
-static int ensure_eng2(smcmi_handle *h, int world, int rank, bool single) {
-    Geo2 g;
-    if (!handle_geo2(h, world, rank, single, &g)) return set_err(SMCMI_ERR_UNSUPPORTED, "engine 2: unsupported shard geometry");
+static int ensure_eng2(smcmi_handle *h, int world, const RunPlan &p) {
+    if (!p.geo_ok) return set_err(SMCMI_ERR_UNSUPPORTED, "engine 2: unsupported shard geometry");
+    const Geo2 &g = p.geo;
     if (h->e2 && h->e2->world == world && h->e2->g.direct == g.direct && h->e2->g.inker == g.inker && h->e2->g.nb2 == g.nb2 && h->e2->g.v0 == g.v0 && h->e2->g.t2 == g.t2 && h->e2->g.nb1 == g.nb1 && h->e2->g.wide == g.wide && h->e2->g.V == g.V && h->e2->g.nv == g.nv) return 0;
     if (h->e2) { free_eng2(h->e2); h->e2 = nullptr; }
     Eng2 *e = new Eng2();
@@ -168,31 +83,6 @@ static int ensure_eng2(smcmi_handle *h, int world, int rank, bool single) {
     return 0;
 }
 
-// Engine 2 serves n_para <= 10: one handle while its cloud is small enough for the direct geometry (every block totals the rows
-// itself: the latency-bound regime engine 2 was built for), and every multi-handle run (one all-gather of V rows per hand-over,
-// results independent of the number of handles).  A single handle with a larger cloud keeps engine 1: its kernels fill the chip
-// there and one-block set-up launches are cheap next to them (engine 2's reduced geometry measured 10-15 % behind at N >= 1e6).
-// SMCMI_ENGINE=1 / =2 force one engine wherever it can run (development, tests).
-// Two chunks per segment worker (one handle of 126 977 .. 253 952 particles) pay where a stage is hand-overs and serial work, not likelihood
-// evaluations: α = 1, one block, one MH step, a likelihood that is a handful of flops per datum.  (Measured in round 5: the 10-dim Gaussian at
-// 250 000 particles 47.5 against engine 1's 63 µs per stage; config 4 - CAPM, three MH steps - 30.6 against 29.6 ms per run: MH-bound runs stay on engine 1.)
-static bool two_chunk_run(const smcmi_handle *h, const smcmi_run_config *rc) {
-    auto cheap = [](int fam) { return fam == SMCMI_LIK_GAUSS_ISO || fam == SMCMI_LIK_LINREG || fam == SMCMI_LIK_NONE; };
-    return rc && rc->alpha == 1.0 && h->d <= 10 && rc->n_blocks == 1 && rc->n_mh_steps == 1 && cheap(h->h_model.lik[0].family) && cheap(h->h_model.lik[1].family);
-}
-static bool eng2_eligible(const smcmi_handle *h, int world, bool single, const smcmi_run_config *rc) {
-    static const int eng = getenv("SMCMI_ENGINE") ? atoi(getenv("SMCMI_ENGINE")) : 0;
-    if (eng == 1 || h->d > 16) return false;
-    Geo2 g;
-    if (!handle_geo2(h, world, 0, single, &g)) return false;
-    // (one handle with more than 256 - V blocks: only the two-chunk segments make engine 2's geometry worth it there)
-    if (single && world == 1 && g.direct && (long long)g.nb2 * g.V > 256 - V2_MAXV && !two_chunk_run(h, rc) && eng != 2) return false;
-    if (g.wide) {                     // n_para 11 .. 16: the same two-launch stage around the generic mutation body (SMCMI_ENGINE=1: engine 1's stage)
-        return true;
-    }
-    return eng == 2 || world > 1 || !single || g.direct;      // (a communicator of one rank is a sharded run: the measurement vehicle for one rank's share)
-}
-
 // the row totals of K1 / K2 are taken by the last block of each virtual shard instead of a k2_reduce launch, while the mutation
 // kernel has at most ~4 blocks per CU (the ticket costs every block two barriers and an atomic: 48.1 vs 50.8 µs per stage at
 // 125 000 particles per handle, but 52.7 vs 46.7 ms per run at 10⁶ on one handle: beyond 2048 blocks k2_reduce launches total the rows)
@@ -213,29 +103,20 @@ static bool fused_tails(const Eng2 *e) {
 #include "mailbox.hpp"
 #include "prof2.hpp"
 
-// Engine 3 serves a single handle in the direct geometry whose blocks are all resident at one per CU; the first use runs the residency
-// self-test (k3_census) and a failure - or SMCMI_ENGINE3=0 - leaves the handle on engine 2's launches for good.
+// Engine 3 serves a handle whose plan has a segment shape (route.hpp: all blocks resident at one per CU); the first use runs the residency
+// self-test (k3_census) and a failure leaves the handle on engine 2's launches for good.
 static int seg3_time_out_words(smcmi_handle *h, double ms) {
     // (in stream order in front of the launches that read the words; the source is a member of the handle: no sync)
     h->e2->h_to3[0] = 0ull; h->e2->h_to3[1] = (unsigned long long)(ms * 1e5);          // 100 MHz wall clock
     HIP_TRY(hipMemcpyAsync(h->e2->d_to3, h->e2->h_to3, sizeof(h->e2->h_to3), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
-static int seg3_ready(smcmi_handle *h, bool *ok, bool two_ok = false) {
+static int seg3_ready(smcmi_handle *h, const RunPlan &p, bool *ok) {
     Eng2 *e = h->e2;
     *ok = false;
-    static const int off = getenv("SMCMI_ENGINE3") ? (atoi(getenv("SMCMI_ENGINE3")) == 0) : 0;
-    const Geo2 &g = e->g;
-    int n_cu = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->cfg.device));
-    // workers + one gatherer per virtual shard, one CU each; a cloud with more 512-particle blocks than that gives every worker two of them
-    // (one handle, a run two_chunk_run admits: `two_ok`)
-    const int ch = (g.Vl * g.nb2 + g.Vl <= n_cu) ? 1 : 2;
-    if (ch == 2 && !two_ok) return 0;
-    const int grid = g.Vl * ((g.nb2 + ch - 1) / ch) + g.Vl;
+    if (!p.seg_chunks || !e->d_rec3) return 0;              // (the shape, or SMCMI_ENGINE3, admits no segment: route.hpp)
+    const int ch = p.seg_chunks, grid = p.seg_grid;
     if (e->seg_ch != ch) { e->seg_ch = ch; if (e->e3_state > 0) e->e3_state = 0; }      // (another grid: the residency self-test again)
-    // (a gatherer totals at most two canonical groups of rows: stage3.hpp gather_vshard)
-    if (off || !(g.direct || g.inker) || g.wide || !e->d_rec3 || g.nb1 != g.nb2 || g.nb2 > 2 * GRP || g.per1 != T3 || g.t2 != T3 || grid > n_cu || h->cfg.max_stages >= 65536) return 0;
     if (e->e3_state < 0) return 0;
     if (e->e3_state == 0) {
         int *d_ok = nullptr;
@@ -253,7 +134,7 @@ static int seg3_ready(smcmi_handle *h, bool *ok, bool two_ok = false) {
         hipFree(d_ok);
         e->e3_state = (okc == grid && fl[0] == 0) ? 1 : -1;
         HIP_TRY(hipMemsetAsync(e->d_tick3, 0, 2 * SEG3_TICKS * sizeof(int), h->stream));
-        if (getenv("SMCMI_TRACE")) fprintf(stderr, "[smcmi3] residency self-test: %d of %d blocks, time-out flag %llu -> engine 3 %s\n", okc, grid, fl[0], e->e3_state > 0 ? "on" : "off");
+        if (sw().trace) fprintf(stderr, "[smcmi3] residency self-test: %d of %d blocks, time-out flag %llu -> engine 3 %s\n", okc, grid, fl[0], e->e3_state > 0 ? "on" : "off");
     }
     *ok = e->e3_state > 0;
     return 0;
@@ -261,17 +142,12 @@ static int seg3_ready(smcmi_handle *h, bool *ok, bool two_ok = false) {
 
 static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *res) {
     smcmi_handle *h0 = g.hs[0];
-    const int nf = h0->h_model.n_free, d = h0->d;
-    if (rc->n_blocks < 1 || rc->n_blocks > nf || ((nf + rc->n_blocks - 1) / rc->n_blocks) * (rc->n_blocks - 1) >= nf)
-        return set_err(SMCMI_ERR_ARG, "n_blocks incompatible with the number of free parameters");
-    if (rc->n_phi < 2 || rc->n_mh_steps < 1) return set_err(SMCMI_ERR_ARG, "bad n_phi / n_mh_steps");
-    if (rc->resampling_method != SMCMI_RESAMPLE_SYSTEMATIC && rc->resampling_method != SMCMI_RESAMPLE_MULTINOMIAL)
-        return set_err(SMCMI_ERR_ARG, "Invalid resampler in SMC. Options are systematic or multinomial");
+    const int d = h0->d;
+    for (auto *h : g.hs) { if (int e = check_run_config(h, rc)) return e; }
     const bool adaptive = !rc->use_fixed_schedule;
     const bool multi = g.world > 1;
     const bool cont = rc->continue_run != 0;
-    std::vector<double> sched(rc->n_phi);
-    for (int k = 0; k < rc->n_phi; ++k) sched[k] = pow((double)k / (double)(rc->n_phi - 1), rc->lambda);
+    const std::vector<double> sched = make_schedule(rc);
     // Fixed schedules (the reference's default, src/smc_main.jl:139,386-387): the energy shift of a stage's incremental weights lags the cloud's
     // largest energy by one mutation (stage2.hpp Begin2::e_seen), so that inside a persistent segment a stage is ONE hand-over (stage3.hpp
     // k3_rides).  The rule belongs to the run, not to the engine: launches, segments and any number of handles apply it alike and leave the
@@ -279,80 +155,49 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     // bound the weights by 1: should a stage's sums overflow (the cloud's largest energy grew by more than ~350 / (ϕ_n - ϕ_{n-1}) in one
     // mutation), the run goes on from that stage with the exact shift (below, at the batch's sync).  SMCMI_SHIFT_LAG=0: exact shifts from the
     // start; =<k >= 3> (development): stage k's lagged shift is made to overflow, =<-k>: to underflow.
-    static const int lag_env = getenv("SMCMI_SHIFT_LAG") ? atoi(getenv("SMCMI_SHIFT_LAG")) : 1;
+    const int lag_env = sw().shift_lag;
     bool shift_lag = !adaptive && lag_env != 0;
     // the shift of the chain's first moments (kernels.hpp k_center_probe): taken from the cloud before the set-up below, applied behind each push
     if (g.world > MAX_SHARDS) return set_err(SMCMI_ERR_ARG, "too many shards");
     const bool alone = g.world == 1 && g.hs.size() == 1;            // (one handle: center_single behind its push, below)
     if (!alone) { if (int e = center_group(g, !cont)) return e; }
     // ---- per-handle set-up: run parameters and the stage-1 state in DevState (as engine 1), then imported into Ctl2
-    for (auto *h : g.hs) {
+    std::vector<RunPlan> plans(g.hs.size());
+    for (auto *&h : g.hs) {
         HIP_TRY(hipSetDevice(h->cfg.device));
-        if (!adaptive && rc->n_phi > h->cfg.max_stages) return set_err(SMCMI_ERR_CAPACITY, "max_stages < n_phi");
         const int rank = multi ? (g.rccl ? h->rank : shard_rank(h)) : 0;
-        if (int e = ensure_eng2(h, g.world, rank, g.hs.size() == 1 && !g.rccl)) return e;
+        RunPlan &p = plans[&h - &g.hs[0]];
+        if (int e = handle_plan(h, g.world, rank, (int)g.hs.size(), g.rccl, true, rc, &p)) return e;
+        if (int e = ensure_eng2(h, g.world, p)) return e;
         if (multi && ensure_shard_buffers(h)) return SMCMI_ERR_HIP;
         // (a fresh run rebuilds the loop state from scratch: only a continuation needs what the device holds - one 70 KB copy and a host
         // round trip less at the start of every run)
         if ((cont && pull_state(h)) || upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
-        DevState &s = h->h_st;
-        RunParams rp{};
-        rp.n_parts = h->cfg.n_parts; rp.n_blocks = rc->n_blocks; rp.n_mh_steps = rc->n_mh_steps; rp.n_phi = rc->n_phi;
-        rp.resampling_method = rc->resampling_method; rp.use_fixed_schedule = rc->use_fixed_schedule;
-        rp.threshold = rc->threshold_ratio * (double)h->cfg.n_parts;
-        rp.alpha = rc->alpha; rp.target = rc->target; rp.tempering_target = rc->tempering_target;
-        rp.pw = rc->tempered_update_prior_weight; rp.logp_old = rc->log_prob_old_data;
-        rp.max_stages = h->cfg.max_stages; rp.store_history = h->cfg.store_history;
-        rp.stall_on_exhaust = 1;
-        rp.phi_rtol = rc->phi_rtol > 0.0 ? rc->phi_rtol : (rc->phi_rtol < 0.0 ? 0.0 : DEFAULT_PHI_RTOL);
-        rp.stop_stage = rc->stop_after_stage > 0 ? rc->stop_after_stage : 0;
+        RunParams rp = make_run_params(h, rc);
         rp.shift_lag = shift_lag ? (lag_env < 0 ? lag_env : std::max(lag_env, 1)) : 0;
-        if (cont) {
-            if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
-            if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");
-            if (s.stage != h0->h_st.stage) return set_err(SMCMI_ERR_STATE, "shards hold different loop states");
-            s.rp = rp; s.done = 0; s.err = 0; s.skip_fold = 1; s.do_resample = 0;
-        } else {
-            const int cur = s.cur;
-            memset(&s, 0, sizeof(DevState));
-        s.e_seen = __builtin_nan("");
-            s.rp = rp; s.cur = cur;
-            s.stage = 1; s.j = 2;                                   // i = 1, j = 2 (smc_main.jl:198-199)
-            s.c = rc->c; s.accept = rc->target;                     // initialize_cloud_settings!, initialization.jl:196-211
-            s.ess_prev = rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts;
-        }
-        if (push_state(h)) return SMCMI_ERR_HIP;
+        // (a continuation goes on from the largest energy the last begin saw: Begin2::e_seen stays)
+        if (int e = start_state(h, rc, rp, true)) return e;
+        if (cont && h->h_st.stage != h0->h_st.stage) return set_err(SMCMI_ERR_STATE, "shards hold different loop states");
         if (alone) { if (int e = center_single(h, !cont)) return e; }
         else center_apply(h);
-        if (!cont) {
-            HIP_TRY(hipMemsetAsync(h->rec.resampled, 0, sizeof(int) * h->cfg.max_stages, h->stream));
-            if (h->cfg.store_history) {
-                HIP_TRY(hipMemsetAsync(h->d_hist_w, 0, sizeof(double) * h->n, h->stream));
-                launch_copy_f64(h->d_hist_W, h->cl.buf[0] + (long long)(h->R - 1) * h->n, h->n, h->stream);
-            }
-        }
+        if (!cont) { if (int e = first_records(h, rc, true)) return e; }
         // (the run's first records ride on the import kernel: four 8-byte host copies and a stream sync less per run)
-        k2_state<<<1, 64, 0, h->stream>>>(h->d_st, h->e2->d_ctl, 1, h->rec, cont ? 0 : 1, rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts, rc->c, rc->target);
+        k2_state<<<1, 64, 0, h->stream>>>(h->d_st, h->e2->d_ctl, 1, h->rec, cont ? 0 : 1, initial_ess(h, rc), rc->c, rc->target);
         HIP_TRY(hipMemsetAsync(h->e2->d_tick, 0, 2 * V2_MAXV * TICK2_STRIDE * sizeof(int), h->stream));
         // random numbers drawn ahead: while K1 leaves most CUs idle (small clouds = the direct geometry with 512-thread mutation blocks)
         Eng2 *e = h->e2;
         e->rng_ahead = false; e->z_ahead = 0; e->n_steps = rc->n_mh_steps; e->n_blocks = rc->n_blocks;
         if (e->g.inker && e->g.t2 == 512 && e->g.Vl * e->g.nb1 <= 160) {
-            const size_t need = (size_t)h->n * (size_t)(h->d + 2) * (size_t)rc->n_mh_steps * (size_t)rc->n_blocks;
-            if (need > h->zbuf_cap) {
-                if (h->d_zbuf) { hipFree(h->d_zbuf); h->d_zbuf = nullptr; h->zbuf_cap = 0; }
-                if (dmalloc(&h->d_zbuf, need)) return SMCMI_ERR_HIP;
-                h->zbuf_cap = need;
-            }
+            if (int e2 = grow_zbuf(h, (size_t)h->n * (size_t)(h->d + 2) * (size_t)rc->n_mh_steps * (size_t)rc->n_blocks)) return e2;
             e->rng_ahead = true;
         }
     }
-    if (getenv("SMCMI_PROF2") && !h0->e2->d_prof) {
+    if (sw().prof2.set && !h0->e2->d_prof) {
         // (the buffer's layout: stage2.hpp PROF2_*)
         if (dmalloc(&h0->e2->d_prof, PROF2_WORDS)) return SMCMI_ERR_HIP;
         HIP_TRY(hipMemset(h0->e2->d_prof, 0, PROF2_WORDS * sizeof(long long)));
         HIP_TRY(hipDeviceSynchronize());
-        h0->e2->prof_stage = atoi(getenv("SMCMI_PROF2"));
+        h0->e2->prof_stage = sw().prof2.v;
     }
     const Geo2 g0 = h0->e2->g;
     const int npf = pad2(h0->npairs + 2), np = pad2(h0->npairs);
@@ -361,7 +206,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     // in-process groups only on request (their kernels share one GPU: a consumer spinning on every CU could starve its producers)
     bool mbox = false;
     // (read at every run: a caller that has validated - or lost confidence in - the transport can switch it between runs)
-    const int want = getenv("SMCMI_MAILBOX") ? atoi(getenv("SMCMI_MAILBOX")) : -1;                 // -1: default; 2: also with one rank (tests)
+    const int want = sw().per_run().mailbox;                 // -1: default; 2: also with one rank (tests)
     for (auto *h : g.hs) h->mbox_used = false;
     // large shards (stage2b.hpp): 256-particle mutation blocks, the stage's serial work in helper blocks that take their hand-over from the mailbox
     const bool big = !inker && !g0.wide && d <= 10;
@@ -371,24 +216,17 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         if (g.rccl) { if (want != 0) { if (int e = mbox_setup_remote(g)) return e; } mbox = h0->mbox_ok && want != 0; }
         else if (want == 1 || self_mb) { if (int e = mbox_setup_group(g)) return e; mbox = true; }
     }
-    static const int big_helpers = getenv("SMCMI_E2_HELPERS") ? atoi(getenv("SMCMI_E2_HELPERS")) : 1;      // development: 0 = k2_begin / k2_prepare as launches
-    const bool bighelp = big && mbox && big_helpers != 0;
+    const bool bighelp = big && mbox && sw().e2_helpers != 0;      // (development: 0 = k2_begin / k2_prepare as launches)
     if (bighelp) {
         // the first proposals' random numbers are drawn by blocks of K1 that follow the correction blocks onto the CUs and run under the helper
-        // block's serial work: as many proposals per particle as fit that window (SMCMI_RNG_AHEAD_PART draws, default 250 000: engine 1's measure)
-        static const long long part = getenv("SMCMI_RNG_AHEAD_PART") ? atoll(getenv("SMCMI_RNG_AHEAD_PART")) : 250000;
+        // block's serial work: as many proposals per particle as fit that window (SMCMI_RNG_AHEAD_PART draws: engine 1's measure, ensure_zbuf)
         for (auto *h : g.hs) {
             Eng2 *e = h->e2;
-            const int za = (int)std::min<long long>((long long)rc->n_mh_steps * rc->n_blocks, part / std::max<long long>(1, h->n));
+            const int za = (int)std::min<long long>((long long)rc->n_mh_steps * rc->n_blocks, sw().rng_ahead_part / std::max<long long>(1, h->n));
             e->z_ahead = 0;
             if (za < 1) continue;
             HIP_TRY(hipSetDevice(h->cfg.device));
-            const size_t need = (size_t)h->n * (size_t)(h->d + 2) * (size_t)za;
-            if (need > h->zbuf_cap) {
-                if (h->d_zbuf) { hipFree(h->d_zbuf); h->d_zbuf = nullptr; h->zbuf_cap = 0; }
-                if (dmalloc(&h->d_zbuf, need)) return SMCMI_ERR_HIP;
-                h->zbuf_cap = need;
-            }
+            if (int e2 = grow_zbuf(h, (size_t)h->n * (size_t)(h->d + 2) * (size_t)za)) return e2;
             e->rng_ahead = true; e->z_ahead = za;
         }
     }
@@ -465,20 +303,17 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
 
     // ---- engine 3: runs of stages that neither resample nor need a certificate pass become one persistent launch each
     bool e3 = false;
-    if (!multi && !g.rccl && g.hs.size() == 1) { if (int e = seg3_ready(h0, &e3, two_chunk_run(h0, rc))) return e; }
+    if (!multi && !g.rccl && g.hs.size() == 1) { if (int e = seg3_ready(h0, plans[0], &e3)) return e; }
     // several handles: the segments span them when the peer mailbox is up (the gatherers post their shard totals into every handle's
     // tables, stage3.hpp Seg3Args::peers) and every handle's grid passed its residency self-test - all ranks must take the same decision
-    static const int e3_env = getenv("SMCMI_ENGINE3") ? atoi(getenv("SMCMI_ENGINE3")) : 1;       // 0 off, 1 default, 2 one handle only, 3 also for in-process groups of any size
-    const int e3_multi = e3_env == 2 ? 0 : (e3_env == 3 ? 2 : 1);
-    // (handles of ONE process share the device's few hardware queues: beyond two of them a handle's persistent launch can sit in a queue
-    // in front of the launch it waits for - the in-process group driver, a test vehicle, keeps to launches there; =2 forces segments)
+    // (which groups SMCMI_ENGINE3 and the number of handles in this process admit: route.hpp)
     const bool seg_sys = (multi || g.rccl) && mbox;      // (a one-rank communicator with SMCMI_MAILBOX=2: the measurement vehicle for one rank's share)
-    if (seg_sys && e3_multi && (g.hs.size() <= 2 || e3_multi == 2)) {
+    if (seg_sys && plans[0].seg_agree) {
         double bad = 0.0;
-        for (auto *h : g.hs) {
+        for (size_t q = 0; q < g.hs.size(); ++q) {
             bool ok = false;
-            HIP_TRY(hipSetDevice(h->cfg.device));
-            if (int e = seg3_ready(h, &ok)) return e;
+            HIP_TRY(hipSetDevice(g.hs[q]->cfg.device));
+            if (int e = seg3_ready(g.hs[q], plans[q], &ok)) return e;
             if (!ok) bad += 1.0;
         }
         for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); HIP_TRY(hipMemcpyAsync(h->d_comm, &bad, sizeof(double), hipMemcpyHostToDevice, h->stream)); HIP_TRY(hipStreamSynchronize(h->stream)); }
@@ -491,7 +326,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     std::vector<hipEvent_t> evs3;
     int seg_launches = 0;
     // a stage that must resample does so inside the segment (stage3.hpp SELECTION): one handle, its own tables
-    static const int sel_in_env = getenv("SMCMI_SEG_SELECT") ? atoi(getenv("SMCMI_SEG_SELECT")) : 1;      // development: 0 = the segment leaves, selection as launches
+    // (development, SMCMI_SEG_SELECT=0: the segment leaves, selection as launches)
     // (the workers' blocks must be the selection kernels' blocks: one 512-slot tile per moment row - not so when a cloud is cut into 2 or 4
     // long virtual shards of more than 32 rows, whose gather blocks take two tiles each)
     // Several handles (sharded segments): the same, with what the handles exchange - chunk sums, the cum column, the ancestors' rows - in the
@@ -502,7 +337,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     const bool sel_one = !seg_sys && g.hs.size() == 1 && h0->d_cum != nullptr && sel_lds;
     const bool sel_sys = seg_sys && mbox_sel_words(h0) > 0 && sel_lds && h0->e2->seg_ch == 1;
     // (two chunks per worker - one handle of up to 253 952 particles -: k3_select_two, the chunk in registers through Sel3Args::transit)
-    const bool sel_inside = e3 && (sel_one || sel_sys) && d <= 10 && sel_in_env != 0 && g0.nbg == g0.nb2 && g0.perg == T3;
+    const bool sel_inside = e3 && (sel_one || sel_sys) && d <= 10 && sw().seg_select != 0 && g0.nbg == g0.nb2 && g0.perg == T3;
     if (sel_inside)
       for (auto *hh : g.hs) {
         smcmi_handle *h0 = hh;                                     // (shadows: one Sel3Args per handle)
@@ -539,8 +374,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     std::vector<SegRange> seg_ranges;              // stages each segment launch was enqueued for (error diagnosis)
     if (e3) {
         // (across ranks the first hand-over of a segment also absorbs the skew between the ranks' hosts: a longer bound)
-        static const double to_env = getenv("SMCMI_SEG_TIMEOUT_MS") ? atof(getenv("SMCMI_SEG_TIMEOUT_MS")) : 0.0;
-        const double to_ms = to_env > 0.0 ? to_env : (seg_sys ? 1000.0 : 200.0);
+        const double to_ms = sw().seg_timeout_ms > 0.0 ? sw().seg_timeout_ms : (seg_sys ? 1000.0 : 200.0);
         for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); if (int e = seg3_time_out_words(h, to_ms)) return e; }
         if (seg_sys) {
             // one launch sequence for all handles - the tags (sequence << 16 | stage) must agree - restarted for every run on cleared tables:
@@ -578,7 +412,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             const Tail2 tail = mb_tail(h, 0, h->e2->vt_cm + (size_t)h->e2->g.v0 * npf);
             Prep2Args pb{};
             if (helper && bighelp) {
-                pb.enable = 1; pb.nb = rc->n_blocks; pb.nf = nf; pb.seed = h->cfg.seed; pb.cmrows = cm_rows(h); pb.rec = h->rec;
+                pb.enable = 1; pb.nb = rc->n_blocks; pb.nf = h->h_model.n_free; pb.seed = h->cfg.seed; pb.cmrows = cm_rows(h); pb.rec = h->rec;
                 pb.md = h->d_model; pb.out = h->e2->d_pre;
             }
 #define SMCMI_CALL(D) launch_k2_correct<D>(h, n, begin_done, spec_expected, mr, tail, pb)
@@ -613,8 +447,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         const size_t nloc = (size_t)h0->n;
         if (int e = g.allgather([](smcmi_handle *h) { return (const double *)h->e2->csum; }, [](smcmi_handle *h) { return h->e2->csum_full; },
                                 (size_t)g0.Vl * g0.nb1)) return e;
-        static const char *xchg = getenv("SMCMI_RESAMPLE_EXCHANGE");
-        const bool a2a = !(xchg && !strcmp(xchg, "allgather")) && rc->resampling_method == SMCMI_RESAMPLE_SYSTEMATIC && !(g.hostc && !h0->hostc.alltoallv);
+        const bool a2a = !sw().resample_allgather && rc->resampling_method == SMCMI_RESAMPLE_SYSTEMATIC && !(g.hostc && !h0->hostc.alltoallv);
         bool rs = true;
         std::vector<long long> ranges(2 * (size_t)g.world, -1);            // per needer: the global rows its slots can descend from
         if (a2a) {
@@ -882,10 +715,10 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     const int solver_passes = rc->solver_passes >= 1 ? rc->solver_passes : DEFAULT_SOLVER_PASSES;
     const int first_passes = std::max(solver_passes, FIRST_SOLVER_PASSES);
     const double N_tot = (double)h0->cfg.n_parts, thr = rc->threshold_ratio * N_tot;
-    static const int sel_mode = getenv("SMCMI_NO_SELECT_PREDICT") ? atoi(getenv("SMCMI_NO_SELECT_PREDICT")) : 0;   // development only
+    const int sel_mode = sw().no_select_predict;   // development only
     const bool predict_select = adaptive && sel_mode != 1;
     // predicted ϕ_n needs the solver's objective to be the correction's ESS (no prior weight, quirk Q4) and a tolerance to verify against
-    const bool spec_ok = adaptive && !getenv("SMCMI_NO_PREDICTOR") && rc->tempered_update_prior_weight == 0.0 && !(rc->phi_rtol < 0.0);
+    const bool spec_ok = adaptive && !sw().no_predictor && rc->tempered_update_prior_weight == 0.0 && !(rc->phi_rtol < 0.0);
     bool spec_on = spec_ok;
     int last_spec_stall = -100, spec_strikes = 0, last_solver_stall = -100;
     int dyn_P = solver_passes;
@@ -960,8 +793,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         }
         if (int e = flush_seg()) return e;
         if (int e = read_ctl(&c)) return e;
-        static const int trace = getenv("SMCMI_TRACE") ? atoi(getenv("SMCMI_TRACE")) : 0;                       // development only
-        if (trace) {
+        if (sw().trace) {                       // development only
             const Post2 &tp = c.ps[0].stage >= c.ps[1].stage ? c.ps[0] : c.ps[1];
             fprintf(stderr, "[smcmi2] sync: launched %d  status (code %d, stage %d, err %d)  post (stage %d, phi %.6g, ess %.6g, rs %d)  begin (stage %d, phi %.6g, final %d)  segments %d\n",
                     launched, c.status.code, c.status.stage, c.status.err, tp.stage, tp.phi_n, tp.ess, tp.do_resample, c.bg.stage, c.bg.phi_n, c.bg.final, seg_launches);
@@ -1049,7 +881,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             prepared_stage = begun_stage = -1;
             force_sel = -1; status_pending = false;
             launched = sn - 2 - base;
-            if (getenv("SMCMI_TRACE")) fprintf(stderr, "[smcmi2] stage %d: sums overflowed under the lagged energy shift - exact shifts from here on\n", sn);
+            if (sw().trace) fprintf(stderr, "[smcmi2] stage %d: sums overflowed under the lagged energy shift - exact shifts from here on\n", sn);
             continue;
         }
         if (c.status.code == 1 || c.status.code == 5 || c.status.code == 9) break;
@@ -1087,21 +919,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     if (profile && !evs.empty()) {
         // event pairs bracket dispatch + kernel: calibrate the fixed part around an empty kernel of the same grid (smcmi_run)
         HIP_TRY(hipSetDevice(h0->cfg.device));
-        hipEvent_t c0, c1;
-        hipEventCreate(&c0); hipEventCreate(&c1);
-        double acc_ms = 0.0;
-        int got = 0;
-        for (int r = 0; r < 64; ++r) {
-            k_fill<<<(unsigned)((h0->n + 255) / 256), 256, 0, h0->stream>>>(nullptr, 0, 0.0);      // (an empty launch of the mutation kernel's grid: event-overhead calibration)
-            hipEventRecord(c0, h0->stream);
-            k_fill<<<(unsigned)((h0->n + 255) / 256), 256, 0, h0->stream>>>(nullptr, 0, 0.0);      // (an empty launch of the mutation kernel's grid: event-overhead calibration)
-            hipEventRecord(c1, h0->stream);
-            hipStreamSynchronize(h0->stream);
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, c0, c1) == hipSuccess) { acc_ms += ms; ++got; }
-        }
-        hipEventDestroy(c0); hipEventDestroy(c1);
-        const double over = got ? std::max(0.0, acc_ms / got - 0.0025) : 0.0;
+        const double over = event_overhead_ms(h0);
         for (size_t k = 0; k + 1 < evs.size(); k += 2) {
             float ms = 0.f;
             if (ev_stage[k / 2] >= 0 && ev_stage[k / 2] <= s.stage && hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) {
@@ -1130,10 +948,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         if (!evs3.empty()) res->segment_stages = timed_stages;        // (profile mode: the stages behind kernel_ms_segments)
     }
     for (hipEvent_t e : evs3) hipEventDestroy(e);
-    res->n_stages = s.stage; res->resamples = s.resamples; res->logmdd = s.logz; res->c = s.c; res->accept = s.accept;
-    res->seconds = std::chrono::duration<double>(t1 - t0).count();
-    res->solver_passes = s.solver_passes;
-    res->paused = (s.done == 5) ? 1 : 0;
+    finish_result(res, s, t0, t1);
     if (mbox) {
         // a hand-over that timed out poisoned the sums with NaN: report THAT, not the NaN-ESS message the poisoned sums lead to
         unsigned long long timed_out = 0;

@@ -35,7 +35,7 @@ enum { SMCMI_NCCL_DOUBLE = 8, SMCMI_NCCL_SUM = 0 };   // ncclFloat64, ncclSum
 
 static int load_rccl() {
     if (g_rccl.lib) return 0;
-    const char *cands[] = {getenv("SMCMI_RCCL_PATH"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+    const char *cands[] = {sw().rccl_path.c_str(), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
     for (const char *c : cands) {
         if (!c || !*c) continue;
         g_rccl.lib = dlopen(c, RTLD_NOW | RTLD_GLOBAL);
@@ -312,7 +312,6 @@ struct ShardGroup {
     }
 };
 
-static int run2_guarded(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *res);
 static int ensure_shard_buffers(smcmi_handle *h) {
     const long long N = h->cfg.n_parts;
     if (!h->d_tot_ess) {
@@ -376,13 +375,9 @@ static int center_group(ShardGroup &g, bool fresh) {
 // one stage, phase by phase over all local shards (the phases between collectives are independent per shard)
 static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *res) {
     smcmi_handle *h0 = g.hs[0];
-    const int nf = h0->h_model.n_free;
-    if (rc->n_blocks < 1 || rc->n_blocks > nf || ((nf + rc->n_blocks - 1) / rc->n_blocks) * (rc->n_blocks - 1) >= nf)
-        return set_err(SMCMI_ERR_ARG, "n_blocks incompatible with the number of free parameters");
-    if (rc->n_phi < 2 || rc->n_mh_steps < 1) return set_err(SMCMI_ERR_ARG, "bad n_phi / n_mh_steps");
+    for (auto *h : g.hs) { if (int e = check_run_config(h, rc)) return e; }
     const bool adaptive = !rc->use_fixed_schedule;
     const int P_default = adaptive ? (rc->solver_passes >= 1 ? rc->solver_passes : SHARDED_SOLVER_PASSES) : 0;
-    static const int no_pred = getenv("SMCMI_NO_PREDICTOR") ? atoi(getenv("SMCMI_NO_PREDICTOR")) : 0;   // development only
     // User likelihoods on the host (the reference's default use: smc(loglikelihood::Function, ...) with parallel = true, src/smc_main.jl:118,
     // 472-476): every shard scores the proposals of ITS particles through its registered callback (callback.hpp host_mutation: propose
     // kernel -> closure on the calling thread -> accept kernel), everything else - solver passes, correction, selection, moments,
@@ -392,62 +387,25 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     const bool host_mut = closure_lik(h0), tempered_cb = closure_lik(h0, 1), dev_cb = h0->dcb[0] != nullptr;
     for (auto *h : g.hs)
         if (closure_lik(h) != host_mut || closure_lik(h, 1) != tempered_cb || (h->dcb[0] != nullptr) != dev_cb) return set_err(SMCMI_ERR_STATE, "every shard needs the same likelihood callbacks");
-    const bool predict = adaptive && !no_pred && !host_mut;
-    static const int sel_mode = getenv("SMCMI_NO_SELECT_PREDICT") ? atoi(getenv("SMCMI_NO_SELECT_PREDICT")) : 0;   // development only
+    const bool predict = adaptive && !sw().no_predictor && !host_mut;
+    const int sel_mode = sw().no_select_predict;   // development only
     const bool predict_select = adaptive && can_fuse_post(h0) && sel_mode != 1 && !host_mut;
-    std::vector<double> sched(rc->n_phi);
-    for (int k = 0; k < rc->n_phi; ++k) sched[k] = pow((double)k / (double)(rc->n_phi - 1), rc->lambda);
+    const std::vector<double> sched = make_schedule(rc);
     for (auto *h : g.hs) {
         HIP_TRY(hipSetDevice(h->cfg.device));
-        if (!adaptive && rc->n_phi > h->cfg.max_stages) return set_err(SMCMI_ERR_CAPACITY, "max_stages < n_phi");
         if (ensure_shard_buffers(h) || pull_state(h) || upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
         if (host_mut) { if (int e = dev_cb ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e; h->rng_ahead = false; h->cb_energy = false; h->cb_calls = 0; h->cb_evals = 0; }
         else if (int e = ensure_zbuf(h, rc->n_mh_steps, rc->n_blocks)) return e;
-        DevState &s = h->h_st;
-        RunParams rp{};
-        rp.n_parts = h->cfg.n_parts; rp.n_blocks = rc->n_blocks; rp.n_mh_steps = rc->n_mh_steps; rp.n_phi = rc->n_phi;
-        rp.resampling_method = rc->resampling_method; rp.use_fixed_schedule = rc->use_fixed_schedule;
-        rp.threshold = rc->threshold_ratio * (double)h->cfg.n_parts;
-        rp.alpha = rc->alpha; rp.target = rc->target; rp.tempering_target = rc->tempering_target;
-        rp.pw = rc->tempered_update_prior_weight; rp.logp_old = rc->log_prob_old_data;
-        rp.max_stages = h->cfg.max_stages; rp.store_history = h->cfg.store_history;
-        rp.stall_on_exhaust = 1;
-        rp.phi_rtol = rc->phi_rtol > 0.0 ? rc->phi_rtol : (rc->phi_rtol < 0.0 ? 0.0 : DEFAULT_PHI_RTOL);
-        rp.stop_stage = rc->stop_after_stage > 0 ? rc->stop_after_stage : 0;
-        if (rc->continue_run) {
-            // continue_intermediate (smc_main.jl:334-335,355-361): every shard keeps the loop scalars, records and history it holds
-            // (a paused run, or smcmi_set_loop_state / _set_stage_records / _set_history with the same scalars on every shard)
-            if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
-            if (s.phi_n >= 1.0) return set_err(SMCMI_ERR_STATE, "the run to continue has already reached phi = 1");
-            if (s.stage != h0->h_st.stage) return set_err(SMCMI_ERR_STATE, "shards hold different loop states");
-            s.rp = rp; s.done = 0; s.err = 0; s.skip_fold = 1; s.do_resample = 0;
-            s.e_seen = __builtin_nan("");                       // (as run1.hpp: this path keeps no Begin2::e_seen)
-            if (push_state(h)) return SMCMI_ERR_HIP;
-            continue;
-        }
-        memset(&s, 0, sizeof(DevState));
-        s.e_seen = __builtin_nan("");
-        s.rp = rp;
-        s.stage = 1; s.j = 2; s.c = rc->c; s.accept = rc->target;
-        s.ess_prev = rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts;
-        if (push_state(h)) return SMCMI_ERR_HIP;
-        const double v0[4] = {0.0, rc->initial_ess > 0.0 ? rc->initial_ess : (double)h->cfg.n_parts, rc->c, rc->target};
-        HIP_TRY(hipMemcpy(h->rec.phi, &v0[0], sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->rec.ess, &v0[1], sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->rec.c, &v0[2], sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->rec.accept, &v0[3], sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(h->rec.resampled, 0, sizeof(int) * h->cfg.max_stages, h->stream));
-        if (h->cfg.store_history) {
-            HIP_TRY(hipMemsetAsync(h->d_hist_w, 0, sizeof(double) * h->n, h->stream));
-            HIP_TRY(hipMemcpyAsync(h->d_hist_W, h->cl.buf[0] + (long long)(h->R - 1) * h->n, sizeof(double) * h->n, hipMemcpyDeviceToDevice, h->stream));
-        }
+        // (a continuation: every shard keeps the loop scalars, records and history it holds - the same scalars on every shard)
+        if (int e = start_state(h, rc, make_run_params(h, rc), false)) return e;
+        if (rc->continue_run) { if (h->h_st.stage != h0->h_st.stage) return set_err(SMCMI_ERR_STATE, "shards hold different loop states"); }
+        else if (int e = first_records(h, rc)) return e;
     }
     if (g.world > MAX_SHARDS) return set_err(SMCMI_ERR_ARG, "too many shards");
     if (int e = center_group(g, !rc->continue_run)) return e;
     for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); center_apply(h); }
     // stage 1's energy shift: largest energy of the initial cloud over all shards (slots after the ES row: a sum all-reduce
     // in which every shard fills only its own slot is a gather)
-    if (g.world > MAX_SHARDS) return set_err(SMCMI_ERR_ARG, "too many shards");
     if (!host_mut) {
     for (auto *h : g.hs) {
         HIP_TRY(hipSetDevice(h->cfg.device));
@@ -564,8 +522,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             }
             // resample redistribution: all-to-all-v of exactly the rows each shard's slots descend from (systematic resampling; the
             // default), or an all-gather of the whole cloud (multinomial resampling, or SMCMI_RESAMPLE_EXCHANGE=allgather)
-            static const char *xchg = getenv("SMCMI_RESAMPLE_EXCHANGE");
-            const bool a2a = rs && !(xchg && !strcmp(xchg, "allgather")) && rc->resampling_method == SMCMI_RESAMPLE_SYSTEMATIC && g.world > 1;
+            const bool a2a = rs && !sw().resample_allgather && rc->resampling_method == SMCMI_RESAMPLE_SYSTEMATIC && g.world > 1;
             if (rs && a2a) {
                 // all-to-all-v redistribution: weights are all-gathered (N doubles), every shard forms the global cumulative sum and
                 // the ancestor range of every shard's slots; then only the rows inside a shard's range travel to it
@@ -757,71 +714,18 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     const auto t1 = std::chrono::steady_clock::now();
     const DevState &s = h0->h_st;
     memset(res, 0, sizeof(*res));
-    res->n_stages = s.stage; res->resamples = s.resamples; res->logmdd = s.logz; res->c = s.c; res->accept = s.accept;
-    res->seconds = std::chrono::duration<double>(t1 - t0).count();
-    res->solver_passes = s.solver_passes;
+    finish_result(res, s, t0, t1);
     res->solver_stalls = stalls; res->select_stalls = sel_stalls; res->spec_stalls = spec_stalls;
-    res->paused = (s.done == 5) ? 1 : 0;
     if (!mut_evs.empty()) {
         // event pairs bracket dispatch + kernel; launches of stalled (no-op) stages are short and rare - they stay in the mean.
         // The dispatch part is calibrated like in smcmi_run: pairs around an empty kernel of the same grid, minus its own ~2.5 µs.
         HIP_TRY(hipSetDevice(h0->cfg.device));
-        hipEvent_t c0, c1;
-        hipEventCreate(&c0); hipEventCreate(&c1);
-        double acc_ms = 0.0;
-        int got = 0;
-        for (int r = 0; r < 64; ++r) {
-            k_fill<<<(unsigned)((h0->n + 255) / 256), 256, 0, h0->stream>>>(nullptr, 0, 0.0);      // (an empty launch of the mutation kernel's grid: event-overhead calibration)
-            hipEventRecord(c0, h0->stream);
-            k_fill<<<(unsigned)((h0->n + 255) / 256), 256, 0, h0->stream>>>(nullptr, 0, 0.0);      // (an empty launch of the mutation kernel's grid: event-overhead calibration)
-            hipEventRecord(c1, h0->stream);
-            hipStreamSynchronize(h0->stream);
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, c0, c1) == hipSuccess) { acc_ms += ms; ++got; }
-        }
-        hipEventDestroy(c0); hipEventDestroy(c1);
-        const double over = got ? std::max(0.0, acc_ms / got - 0.0025) : 0.0;
+        const double over = event_overhead_ms(h0);
         for (size_t k = 0; k + 1 < mut_evs.size(); k += 2) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, mut_evs[k], mut_evs[k + 1]) == hipSuccess) { res->kernel_ms_mutate += std::max(0.0, (double)ms - over); res->n_mutate_launches += 1; }
         }
         for (hipEvent_t e : mut_evs) hipEventDestroy(e);
     }
-    if (s.err) return err_from_state(s.err);
-    if (!s.done) return set_err(SMCMI_ERR_CAPACITY, "max_stages exceeded before the tempering schedule reached 1");
-    return 0;
-}
-
-extern "C" int smcmi_run_sharded(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res) {
-    if (int e = need_model(h, 2)) return e;
-    if (!rc || !res) return set_err(SMCMI_ERR_ARG, "null argument");
-    res->n_segments = 0; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
-    res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
-    if (!h->nccl && !h->has_hostc) return set_err(SMCMI_ERR_STATE, "smcmi_comm_init / smcmi_comm_init_host has not been called on this handle");
-    if (int e = check_lik_pair(h)) return e;
-    if (h->dcb[0]) return set_err(SMCMI_ERR_UNSUPPORTED, "device likelihood callbacks serve one process (smcmi_run, smcmi_run_group); a multi-process run needs host callbacks or a device family");
-    ShardGroup g;
-    g.hs = {h}; g.world = h->world; g.rccl = true; g.hostc = h->has_hostc;
-    if (!closure_lik(h) && eng2_eligible(h, g.world, false, rc)) return run2_guarded(g, rc, res);      // n_para <= 10: the two-launch stage (stage2.hpp / run2.hpp)
-    return run_sharded_impl(g, rc, res);                                             // n_para > 10, and every run with a host likelihood
-}
-
-extern "C" int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, smcmi_result *res) {
-    if (!hs || n < 1 || !rc || !res) return set_err(SMCMI_ERR_ARG, "bad argument");
-    res->n_segments = 0; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
-    res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
-    ShardGroup g;
-    long long expect = 0;
-    for (int k = 0; k < n; ++k) {
-        if (int e = need_model(hs[k], 2)) return e;
-        if (int e = check_lik_pair(hs[k])) return e;
-        if (hs[k]->cfg.gid0 != expect || hs[k]->cfg.n_local != hs[0]->cfg.n_local || hs[k]->cfg.n_parts != hs[0]->cfg.n_parts)
-            return set_err(SMCMI_ERR_ARG, "group handles must be equal contiguous shards in rank order");
-        expect += hs[k]->cfg.n_local;
-        g.hs.push_back(hs[k]);
-    }
-    if (expect != hs[0]->cfg.n_parts) return set_err(SMCMI_ERR_ARG, "group handles do not cover n_parts");
-    g.world = n; g.rccl = false;
-    if (!closure_lik(hs[0]) && eng2_eligible(hs[0], g.world, n == 1, rc)) return run2_guarded(g, rc, res);
-    return run_sharded_impl(g, rc, res);
+    return finish_error(s);
 }

@@ -7,6 +7,8 @@
 // waits on the GPU inside a stage.  There is NO CPU fallback: every entry point fails with SMCMI_ERR_HIP when no
 // gfx950 device is usable.
 #include "handle.hpp"
+#include "switches.hpp"
+#include "route.hpp"
 
 static void free_eng2(Eng2 *e);
 static void free_callback_buffers(CallbackBuffers *b);
@@ -50,7 +52,7 @@ static int forget_e_seen(smcmi_handle *h) {
 // center_shift turns the gathered rows into the shift; center_apply, enqueued behind the push of the chain's first DevState, puts it there.
 // SMCMI_CENTER=0 (development): the shift stays what the handle holds - 0 at the head of a run, the last mean it computed otherwise - the
 // arithmetic before the centre was taken from the cloud (tests/test_gpu_moment_range.py records its errors)
-static bool center_on() { static const int on = getenv("SMCMI_CENTER") ? atoi(getenv("SMCMI_CENTER")) : 1; return on != 0; }
+static bool center_on() { return sw().center != 0; }
 static inline double *center_rows(smcmi_handle *h) { return h->d_center; }
 static inline double *center_out(smcmi_handle *h) { return h->d_center + (size_t)CENTER_SLOTS * (2 * h->d + 1); }
 static int center_probe(smcmi_handle *h, int rank, int world) {
@@ -110,7 +112,7 @@ static int dmalloc(T **p, size_t count) {
     HIP_TRY(hipMalloc((void **)p, (count ? count : 1) * sizeof(T)));
     // development (SMCMI_POISON_ALLOC=1): fresh device memory reads as NaN / -1, so a read of something never written shows up
     // in every test instead of depending on what the allocator hands back
-    static const int poison = getenv("SMCMI_POISON_ALLOC") ? atoi(getenv("SMCMI_POISON_ALLOC")) : 0;
+    const int poison = sw().poison_alloc;
     static int counter = 0;
     const int idx = counter++;
     if (poison) {
@@ -327,10 +329,9 @@ extern "C" int smcmi_set_parameters(smcmi_handle *h, const int32_t *fixed, const
 // old likelihood is the same state-space model: the Kalman filter over the data passes through the old data's log-likelihood on
 // its way (bit for bit: same x_0, P_0, same steps), so the mutation evaluates one filter instead of two (SMCMI_NO_LIK_PREFIX=1 keeps two).
 static void update_lik_prefix(smcmi_handle *h) {
-    static const int off = getenv("SMCMI_NO_LIK_PREFIX") ? atoi(getenv("SMCMI_NO_LIK_PREFIX")) : 0;
     const LikDev &a = h->h_model.lik[0], &b = h->h_model.lik[1];
     const std::vector<double> &da = h->lik_host_data[0], &db = h->lik_host_data[1];
-    bool ok = !off && a.family == SMCMI_LIK_LGSS_KALMAN && b.family == SMCMI_LIK_LGSS_KALMAN && a.rows == b.rows && b.cols >= 1 && b.cols <= a.cols &&
+    bool ok = !sw().no_lik_prefix && a.family == SMCMI_LIK_LGSS_KALMAN && b.family == SMCMI_LIK_LGSS_KALMAN && a.rows == b.rows && b.cols >= 1 && b.cols <= a.cols &&
               a.n_par == b.n_par && !da.empty() && !db.empty() && h->lik_host_aux[0] == h->lik_host_aux[1];
     for (int k = 0; ok && k < a.n_par; ++k) ok = a.par[k] == b.par[k];
     if (ok) ok = memcmp(da.data(), db.data(), sizeof(double) * db.size()) == 0;
@@ -849,20 +850,18 @@ static void launch_reg(smcmi_handle *h, const MutArgs &ma, int standalone) {
 }
 static int set_mutate_attrs(smcmi_handle *) { return 0; }   // the register kernel needs < 64 KiB of dynamic LDS
 static bool use_reg_mutate(const smcmi_handle *h) { return h->d <= 10; }
-// lgss_kalman on both vintages (or no old vintage) and at most 32 768 particles on the handle: four lanes per particle (kernels.hpp
-// k_mutate<0, 4>) - up to two of its wavefronts per SIMD; beyond that one thread per particle (fewer instructions per particle) is
-// faster (measured: §6 of DESIGN.md).  SMCMI_KALMAN_LANES=1 / 4 forces one or the other (development / comparison).
-static bool use_ls4_mutate(const smcmi_handle *h) {
-    static const int lanes = getenv("SMCMI_KALMAN_LANES") ? atoi(getenv("SMCMI_KALMAN_LANES")) : 0;
-    const int f0 = h->h_model.lik[0].family, f1 = h->h_model.lik[1].family;
-    if (!(h->d == 13 && f0 == SMCMI_LIK_LGSS_KALMAN && (f1 == SMCMI_LIK_NONE || f1 == SMCMI_LIK_LGSS_KALMAN))) return false;
-    return lanes == 4 || (lanes != 1 && h->n <= 32768);
+// what route.hpp asks of a handle by itself: its cloud, its model, its capacity (handle_plan, run2.hpp, adds the run's communicator)
+static RunShape handle_shape(const smcmi_handle *h) {
+    RunShape r;
+    r.N = h->cfg.n_parts; r.n = h->n; r.d = h->d; r.max_stages = h->cfg.max_stages;
+    r.lik0 = h->h_model.lik[0].family; r.lik1 = h->h_model.lik[1].family;
+    r.closure = closure_lik(h);
+    return r;
 }
-// the same models on larger clouds: one thread per particle through kalman_lgss_wave
-static bool use_wave_kalman(const smcmi_handle *h) {
-    const int f0 = h->h_model.lik[0].family, f1 = h->h_model.lik[1].family;
-    return !use_ls4_mutate(h) && h->d == 13 && f0 == SMCMI_LIK_LGSS_KALMAN && (f1 == SMCMI_LIK_NONE || f1 == SMCMI_LIK_LGSS_KALMAN);
-}
+// lgss_kalman on a small cloud: four lanes per particle (the rule: route.hpp route_ls4) ...
+static bool use_ls4_mutate(const smcmi_handle *h) { return route_ls4(handle_shape(h), sw()); }
+// ... the same models on larger clouds: one thread per particle through kalman_lgss_wave
+static bool use_wave_kalman(const smcmi_handle *h) { return kalman_model(handle_shape(h)) && !use_ls4_mutate(h); }
 // blocks (= rows of acceptance / energy partials) of the in-run mutation kernel
 static int mut_blocks(const smcmi_handle *h) { return use_reg_mutate(h) ? h->nb_reg : (use_ls4_mutate(h) ? h->nb_mut_ls4 : h->nb_mut); }
 // returns the number of blocks launched (= acceptance partials written)
@@ -875,8 +874,7 @@ static int launch_mutate(smcmi_handle *h, int n_blocks, int standalone, double a
     ma.debug = dbg;
     ma.stage_consts = (h->d <= 13 && !(dbg & 512)) ? 1 : 0;
     ma.prof = h->d_prof;
-    static const int no_pred = getenv("SMCMI_NO_PREDICTOR") ? atoi(getenv("SMCMI_NO_PREDICTOR")) : 0;   // development only
-    ma.esum = (!standalone && h->run_adaptive && !no_pred) ? h->d_esum_part : nullptr;
+    ma.esum = (!standalone && h->run_adaptive && !sw().no_predictor) ? h->d_esum_part : nullptr;
     ma.emax = !standalone ? h->d_emax_part : nullptr;
     ma.zbuf = (!standalone && h->rng_ahead && use_reg_mutate(h)) ? h->d_zbuf : nullptr;
     ma.z_ahead = h->z_ahead;
@@ -988,6 +986,13 @@ extern "C" int smcmi_accept(smcmi_handle *h, const double *loglik_new, const dou
 
 // In-run proposal set-up: block 0 prepares the proposal, the other blocks draw the stage's random numbers ahead (RngAhead) when
 // the register mutation kernel will run and the buffer fits.  from_totals as in k_prepare_mutation.
+static int grow_zbuf(smcmi_handle *h, size_t need) {
+    if (need <= h->zbuf_cap) return 0;
+    if (h->d_zbuf) { hipFree(h->d_zbuf); h->d_zbuf = nullptr; h->zbuf_cap = 0; }
+    if (dmalloc(&h->d_zbuf, need)) return SMCMI_ERR_HIP;
+    h->zbuf_cap = need;
+    return 0;
+}
 static int ensure_zbuf(smcmi_handle *h, int n_mh_steps, int n_blocks) {
     h->rng_ahead = false;
     if (!use_reg_mutate(h)) return 0;
@@ -997,18 +1002,12 @@ static int ensure_zbuf(smcmi_handle *h, int n_mh_steps, int n_blocks) {
     // mutation kernel: up to 250 000 particle-proposals - about what the set-up launch's idle window (~10 µs on 255 CUs) absorbs.
     // Config 4 (3 proposals for each of 200 000 particles) per run: none ahead 30.5 ms, one 29.6-29.8, two 30.2-30.3, all three 30.7.
     const long long ahead_max = 500000;
-    static const long long part_max = getenv("SMCMI_RNG_AHEAD_PART") ? atoll(getenv("SMCMI_RNG_AHEAD_PART")) : 250000;  // development only
     const int props = n_mh_steps * n_blocks;
     int k_ahead = props;
-    if ((long long)h->n * props > ahead_max) k_ahead = (int)std::min<long long>(props, part_max / (long long)h->n);
+    if ((long long)h->n * props > ahead_max) k_ahead = (int)std::min<long long>(props, sw().rng_ahead_part / (long long)h->n);
     h->z_ahead = k_ahead;
     if (k_ahead < 1) return 0;
-    const size_t need = (size_t)h->n * (size_t)(h->d + 2) * (size_t)k_ahead;
-    if (need > h->zbuf_cap) {
-        if (h->d_zbuf) { hipFree(h->d_zbuf); h->d_zbuf = nullptr; h->zbuf_cap = 0; }
-        if (dmalloc(&h->d_zbuf, need)) return SMCMI_ERR_HIP;
-        h->zbuf_cap = need;
-    }
+    if (int e = grow_zbuf(h, (size_t)h->n * (size_t)(h->d + 2) * (size_t)k_ahead)) return e;
     h->rng_ahead = true;
     return 0;
 }
@@ -1030,6 +1029,7 @@ static void launch_prepare_in_run(smcmi_handle *h, const double *partials, int n
                                                              sol_slot, h->rec, pr, h->note_on ? h->d_note : nullptr);
 }
 
+#include "runsetup.hpp"
 #include "run1.hpp"
 
 extern "C" int smcmi_stages_held(smcmi_handle *h, int32_t *n_stages_out) {
@@ -1244,12 +1244,11 @@ extern "C" int smcmi_callback_phases(smcmi_handle *h, double *ms_out, int32_t n)
 // A group of handles (sharded segments, run2.hpp) does the same: a hand-over that ran out anywhere stops that rank's posts, so every rank's
 // run ends in the time-out and every rank repeats - the same decision everywhere without an exchange.
 static int run2_guarded(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *res) {
-    static const int e3_off = getenv("SMCMI_ENGINE3") ? (atoi(getenv("SMCMI_ENGINE3")) == 0) : 0;
-    static const int e3_sharded = getenv("SMCMI_ENGINE3") ? (atoi(getenv("SMCMI_ENGINE3")) != 2) : 1;
     smcmi_handle *h0 = g.hs[0];
-    const bool single = g.world == 1 && !g.rccl && g.hs.size() == 1;
-    bool may_seg = !e3_off && h0->d <= 10 && (single || e3_sharded);
-    for (auto *h : g.hs) may_seg = may_seg && h->n <= (single ? 253952 : 131072) && (!h->e2 || h->e2->e3_state >= 0);
+    RunPlan p0;                           // (the handles of a group are equal shards: one plan's `snapshot` speaks for all)
+    if (int e = handle_plan(h0, g.world, 0, (int)g.hs.size(), g.rccl, true, rc, &p0)) return e;
+    bool may_seg = p0.snapshot;
+    for (auto *h : g.hs) may_seg = may_seg && (!h->e2 || h->e2->e3_state >= 0);
     const long long state_n = (long long)((sizeof(DevState) + 7) / 8);     // (doubles)
     if (may_seg) {
         for (auto *h : g.hs) {
@@ -1265,7 +1264,7 @@ static int run2_guarded(ShardGroup &g, const smcmi_run_config *rc, smcmi_result 
     for (auto *h : g.hs) stale.push_back(h->center_stale);
     int e = run2_impl(g, rc, res);
     if (e == SMCMI_ERR_TIMEOUT && may_seg && h0->e2 && h0->e2->e3_state < 0) {
-        if (getenv("SMCMI_TRACE")) fprintf(stderr, "[smcmi3] segment time-out: the run is repeated as launches from the cloud it started with\n");
+        if (sw().trace) fprintf(stderr, "[smcmi3] segment time-out: the run is repeated as launches from the cloud it started with\n");
         for (auto *h : g.hs) {
             const long long cloud_n = (long long)h->n * h->R;
             HIP_TRY(hipSetDevice(h->cfg.device));
@@ -1279,10 +1278,57 @@ static int run2_guarded(ShardGroup &g, const smcmi_run_config *rc, smcmi_result 
     }
     return e;
 }
-static int run2_single(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res) {
-    ShardGroup g;
+extern "C" int smcmi_run(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res) {
+    if (int e = need_model(h, 2)) return e;
+    if (!rc || !res) return set_err(SMCMI_ERR_ARG, "null argument");
+    if (h->cfg.n_local != h->cfg.n_parts) return set_err(SMCMI_ERR_UNSUPPORTED, "smcmi_run drives a single shard; use the shard-level calls for multi-GPU");
+    res->n_segments = 0; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
+    res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
+    if (int e = check_lik_pair(h)) return e;
+    RunPlan p;
+    if (int e = handle_plan(h, 1, 0, 1, false, false, rc, &p)) return e;
+    if (p.driver == DRIVER_CALLBACK) return run_callback(h, rc, res);       // user likelihood: a host callback or a device callback (callback.hpp)
+    if (p.driver != DRIVER_ENGINE2) return run1_impl(h, rc, res);
+    ShardGroup g;                                                           // n_para <= 10: the two-launch stage (stage2.hpp)
     g.hs = {h}; g.world = 1; g.rccl = false;
     return run2_guarded(g, rc, res);
+}
+extern "C" int smcmi_run_sharded(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *res) {
+    if (int e = need_model(h, 2)) return e;
+    if (!rc || !res) return set_err(SMCMI_ERR_ARG, "null argument");
+    res->n_segments = 0; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
+    res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
+    if (!h->nccl && !h->has_hostc) return set_err(SMCMI_ERR_STATE, "smcmi_comm_init / smcmi_comm_init_host has not been called on this handle");
+    if (int e = check_lik_pair(h)) return e;
+    if (h->dcb[0]) return set_err(SMCMI_ERR_UNSUPPORTED, "device likelihood callbacks serve one process (smcmi_run, smcmi_run_group); a multi-process run needs host callbacks or a device family");
+    ShardGroup g;
+    g.hs = {h}; g.world = h->world; g.rccl = true; g.hostc = h->has_hostc;
+    RunPlan p;
+    if (int e = handle_plan(h, g.world, 0, 1, true, true, rc, &p)) return e;
+    if (p.driver == DRIVER_ENGINE2) return run2_guarded(g, rc, res);                 // n_para <= 10: the two-launch stage (stage2.hpp / run2.hpp)
+    return run_sharded_impl(g, rc, res);                                             // n_para > 10, and every run with a host likelihood
+}
+
+extern "C" int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, smcmi_result *res) {
+    if (!hs || n < 1 || !rc || !res) return set_err(SMCMI_ERR_ARG, "bad argument");
+    res->n_segments = 0; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
+    res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
+    ShardGroup g;
+    long long expect = 0;
+    for (int k = 0; k < n; ++k) {
+        if (int e = need_model(hs[k], 2)) return e;
+        if (int e = check_lik_pair(hs[k])) return e;
+        if (hs[k]->cfg.gid0 != expect || hs[k]->cfg.n_local != hs[0]->cfg.n_local || hs[k]->cfg.n_parts != hs[0]->cfg.n_parts)
+            return set_err(SMCMI_ERR_ARG, "group handles must be equal contiguous shards in rank order");
+        expect += hs[k]->cfg.n_local;
+        g.hs.push_back(hs[k]);
+    }
+    if (expect != hs[0]->cfg.n_parts) return set_err(SMCMI_ERR_ARG, "group handles do not cover n_parts");
+    g.world = n; g.rccl = false;
+    RunPlan p;
+    if (int e = handle_plan(hs[0], g.world, 0, n, false, true, rc, &p)) return e;
+    if (p.driver == DRIVER_ENGINE2) return run2_guarded(g, rc, res);
+    return run_sharded_impl(g, rc, res);
 }
 
 

@@ -144,3 +144,43 @@ def test_header_is_plain_c_and_the_c_example_links(libmod, tmp_path):
                         os.path.join(ROOT, "examples", "c_abi_config2.c"), "-L", os.path.join(ROOT, "smc.jl_amd", "csrc"), "-lsmcmi", "-lm",
                         "-Wl,-rpath-link,/opt/rocm/lib", "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+def test_routing_table_is_the_one_the_hand_written_predicates_gave(tmp_path):
+    """csrc/route.hpp decides where a run goes (driver, engine 2's geometry, Kalman lanes, segment shape).  tests/route_check.hip prints
+    its table for every boundary of the geometry under six switch sets - host code, no device - and the table must equal the one
+    recorded from the predicates route.hpp replaced (tests/golden/routing_table.txt)."""
+    import subprocess
+
+    exe = tmp_path / "route_check"
+    r = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "--offload-host-only", "-O1", "-std=c++17",
+                        os.path.join(ROOT, "tests", "route_check.hip"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = r.stdout.splitlines()
+    want = open(os.path.join(ROOT, "tests", "golden", "routing_table.txt")).read().splitlines()
+    assert len(want) > 1500
+    diff = [(a, b) for a, b in zip(want, got) if a != b]
+    assert not diff, "%d of %d lines differ, the first:\n%s\n%s" % (len(diff), len(want), diff[0][0], diff[0][1])
+    assert len(got) == len(want), (len(got), len(want))
+
+
+def test_switches_hpp_is_the_only_reader_of_the_environment_and_matches_the_design_table():
+    """DESIGN §7b lists the development switches; csrc/switches.hpp reads exactly those names and nothing else under csrc/ reads the
+    environment for one."""
+    csrc = os.path.join(ROOT, "smc.jl_amd", "csrc")
+    read = set(re.findall(r'\("(SMCMI_[A-Z0-9_]+)"', open(os.path.join(csrc, "switches.hpp")).read()))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    m = re.search(r"^## 7b\. (.*?)\n(.*?)^## ", design, re.S | re.M)
+    assert m, "DESIGN.md has no section 7b"
+    count = re.search(r"(\d+) names", m.group(1))
+    rows = [ln for ln in m.group(2).splitlines() if ln.startswith("| `SMCMI_")]
+    listed = set(re.findall(r"SMCMI_[A-Z0-9_]+", "\n".join(ln.split("|")[1] for ln in rows)))
+    assert read == listed, (sorted(read - listed), sorted(listed - read))
+    assert count and int(count.group(1)) == len(listed), (count and count.group(1), len(listed))
+    others = []
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hpp", ".hip")) and f != "switches.hpp" and re.search(r'getenv\s*\(\s*"SMCMI_', open(os.path.join(csrc, f)).read()):
+            others.append(f)
+    assert not others, others

@@ -113,3 +113,45 @@ def test_posdef_exception_aborts_the_run(name, env, shards):
     assert r["good_after"][0] == 40 and r["good_after"][1], r
     if name == "segments":
         assert r["good_after"][2] >= 1
+
+
+def test_the_sharded_all_reduce_driver_rejects_an_unknown_resampler():
+    """run_sharded_impl (n_para > 16 behind a group: two handles x 512 particles, n_para = 17) validates the resampler like the other three
+    drivers: resampling_method = 7, set directly on the run configuration, is SMCMI_ERR_ARG with the reference's message before any stage
+    runs - the handles' stage records stay untouched and the next run on the same handles is fine."""
+    import ctypes as C
+
+    import numpy as np
+
+    from smc_jl_amd import Engine, run_group
+    from smc_jl_amd.host import _lib
+    from tests import models
+
+    d, n, nl = 17, 1024, 512
+    spec = models.gauss_spec(d=d, sigma=0.5, prior_sd=2.0)
+    engs = []
+    for k in range(2):
+        e = Engine(n, d, seed=5, max_stages=40, store_history=False, n_local=nl, gid0=k * nl)
+        e.set_model(spec)
+        e.init_from_prior()
+        engs.append(e)
+    kw = dict(use_fixed_schedule=True, n_phi=12)
+    good = run_group(engs, **kw)
+    before = [e.stage_records(good["n_stages"]) for e in engs]
+    rc = engs[0]._run_config(1, 1, 2.1, 12, "systematic", 0.5, 0.5, 1.0, 0.25, True, 0.97, 0.0, 0.0, 0, 0, 0, 0.0)
+    rc.resampling_method = 7
+    res = _lib.Result()
+    arr = (C.c_void_p * 2)(*[e._h for e in engs])
+    code = _lib.lib().smcmi_run_group(arr, 2, C.byref(rc), C.byref(res))
+    msg = _lib.lib().smcmi_last_error().decode()
+    print("code", code, "message", msg)
+    assert code == -1, (code, msg)                                                   # SMCMI_ERR_ARG
+    assert msg == "Invalid resampler in SMC. Options are systematic or multinomial", msg
+    for e, b in zip(engs, before):                                                   # nothing ran: the records are the last run's
+        a = e.stage_records(good["n_stages"])
+        for key in ("schedule", "ess", "c_hist", "accept_hist", "resampled"):
+            np.testing.assert_array_equal(a[key], b[key])
+    again = run_group(engs, **kw)
+    assert again["n_stages"] == 12 and np.isfinite(again["logmdd"])
+    for e in engs:
+        e.close()
