@@ -31,44 +31,33 @@ struct CallbackBuffers {
     hipEvent_t ev_prop = nullptr, ev_up = nullptr, ev_head = nullptr;
     std::vector<hipEvent_t> ev_chunk;
     double phase_ms[CBP_N] = {0, 0, 0, 0, 0, 0, 0, 0};
+    devmem::Owner<> mem;             // the pinned buffers above
+    devmem::Handles made;            // the streams and events above
 };
-static void free_callback_buffers(CallbackBuffers *b) {
-    if (!b) return;
-    void *ptrs[] = {b->h_prop, b->h_lp, b->h_pack, b->h_lik[0], b->h_lik[1], b->h_out, b->h_idx};
-    for (void *p : ptrs)
-        if (p) hipHostFree(p);
-    for (hipEvent_t e : b->ev_chunk) hipEventDestroy(e);
-    if (b->ev_prop) hipEventDestroy(b->ev_prop);
-    if (b->ev_up) hipEventDestroy(b->ev_up);
-    if (b->ev_head) hipEventDestroy(b->ev_head);
-    if (b->s_down) hipStreamDestroy(b->s_down);
-    if (b->s_up) hipStreamDestroy(b->s_up);
-    delete b;
-}
 constexpr int CB_MAX_CHUNKS = 16;
 static int ensure_callback_buffers(smcmi_handle *h) {
     if (h->cbuf && h->cbuf->n == h->n && h->cbuf->d == h->d) return 0;
-    if (h->cbuf) { free_callback_buffers(h->cbuf); h->cbuf = nullptr; }
-    CallbackBuffers *b = new CallbackBuffers();
+    delete h->cbuf;
+    h->cbuf = nullptr;
+    std::unique_ptr<CallbackBuffers> b(new CallbackBuffers());        // (installed only when complete; a failure below destroys it with what it made)
+    b->mem.poison = sw().poison_alloc;
     b->n = h->n; b->d = h->d;
     const size_t n = (size_t)h->n, d = (size_t)h->d;
-    bool ok = hipHostMalloc((void **)&b->h_prop, n * (d + 1) * 8) == hipSuccess && hipHostMalloc((void **)&b->h_lp, n * 8) == hipSuccess &&
-              hipHostMalloc((void **)&b->h_pack, n * d * 8) == hipSuccess && hipHostMalloc((void **)&b->h_lik[0], n * 8) == hipSuccess &&
-              hipHostMalloc((void **)&b->h_lik[1], n * 8) == hipSuccess && hipHostMalloc((void **)&b->h_out, n * 8) == hipSuccess &&
-              hipHostMalloc((void **)&b->h_idx, n * 8) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&b->s_down, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&b->s_up, hipStreamNonBlocking) == hipSuccess &&
-         hipEventCreateWithFlags(&b->ev_prop, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&b->ev_head, hipEventDisableTiming) == hipSuccess;
+    const devmem::Kind pinned = devmem::Kind::Pinned;
+    bool ok = b->mem.alloc(&b->h_prop, n * (d + 1), pinned) == hipSuccess && b->mem.alloc(&b->h_lp, n, pinned) == hipSuccess &&
+              b->mem.alloc(&b->h_pack, n * d, pinned) == hipSuccess && b->mem.alloc(&b->h_lik[0], n, pinned) == hipSuccess &&
+              b->mem.alloc(&b->h_lik[1], n, pinned) == hipSuccess && b->mem.alloc(&b->h_out, n, pinned) == hipSuccess &&
+              b->mem.alloc(&b->h_idx, n, pinned) == hipSuccess;
+    ok = ok && b->made.stream(&b->s_down) == hipSuccess && b->made.stream(&b->s_up) == hipSuccess &&
+         b->made.event(&b->ev_prop, hipEventDisableTiming) == hipSuccess && b->made.event(&b->ev_up, hipEventDisableTiming) == hipSuccess &&
+         b->made.event(&b->ev_head, hipEventDisableTiming) == hipSuccess;
     for (int c = 0; ok && c < CB_MAX_CHUNKS; ++c) {
         hipEvent_t e = nullptr;
-        ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        ok = b->made.event(&e, hipEventDisableTiming) == hipSuccess;
         if (ok) b->ev_chunk.push_back(e);
     }
-    if (!ok) {
-        free_callback_buffers(b);
-        return set_err(SMCMI_ERR_HIP, "hipHostMalloc / stream creation failed (callback staging buffers)");
-    }
-    h->cbuf = b;
+    if (!ok) return set_err(SMCMI_ERR_HIP, "pinned memory / stream creation failed (callback staging buffers)");
+    h->cbuf = b.release();
     return 0;
 }
 // chunks a batch of n proposals crosses PCIe in: K = min(8, n / 12288) chunks of ceil(n / K) particles, the last one possibly shorter (a chunk

@@ -19,25 +19,20 @@ struct DevCallbackBuffers {
     long long *h_cnt = nullptr;      // pinned: where the host reads them
     long long m = 0;                 // of the last count (the old-data callback of a tempered update scores the same batch)
     double phase_ms[CBP_N] = {0, 0, 0, 0, 0, 0, 0, 0};
+    devmem::Owner<> mem;             // the buffers above
 };
-static void free_dev_callback_buffers(DevCallbackBuffers *b) {
-    if (!b) return;
-    void *ptrs[] = {b->d_pack, b->d_out, b->d_pos, b->d_blk, b->d_cnt};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    if (b->h_cnt) hipHostFree(b->h_cnt);
-    delete b;
-}
 static int ensure_dev_callback_buffers(smcmi_handle *h) {
     if (h->dcbuf && h->dcbuf->n == h->n && h->dcbuf->d == h->d) return 0;
-    if (h->dcbuf) { free_dev_callback_buffers(h->dcbuf); h->dcbuf = nullptr; }
-    DevCallbackBuffers *b = new DevCallbackBuffers();
+    delete h->dcbuf;
+    h->dcbuf = nullptr;
+    std::unique_ptr<DevCallbackBuffers> b(new DevCallbackBuffers());  // (installed only when complete; a failure below destroys it with what it made)
+    b->mem.poison = sw().poison_alloc;
     b->n = h->n; b->d = h->d;
     const size_t n = (size_t)h->n, d = (size_t)h->d, nb = (n + TB - 1) / TB;
-    h->dcbuf = b;                    // (owned by the handle from here on: smcmi_destroy frees what was allocated)
-    if (dmalloc(&b->d_pack, n * d) || dmalloc(&b->d_out, n) || dmalloc(&b->d_pos, n) || dmalloc(&b->d_blk, nb + 1) || dmalloc(&b->d_cnt, 2))
+    if (dmalloc(b->mem, &b->d_pack, n * d) || dmalloc(b->mem, &b->d_out, n) || dmalloc(b->mem, &b->d_pos, n) || dmalloc(b->mem, &b->d_blk, nb + 1) || dmalloc(b->mem, &b->d_cnt, 2))
         return SMCMI_ERR_HIP;
-    HIP_TRY(hipHostMalloc((void **)&b->h_cnt, 2 * sizeof(long long)));
+    HIP_TRY(b->mem.alloc(&b->h_cnt, 2, devmem::Kind::Pinned));
+    h->dcbuf = b.release();
     return 0;
 }
 

@@ -10,10 +10,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/smcmi.h"
+#include "devmem.hpp"
 #include "devstate.hpp"
 #include "kernels.hpp"
 #include "stage2.hpp"
@@ -55,6 +57,7 @@ struct Eng2 {
     bool rng_ahead = false;          // K1 carries blocks that draw the mutation's random numbers into the handle's zbuf
     int n_steps = 1, n_blocks = 1;
     int z_ahead = 0;                 // large shards: proposals per particle the drawing blocks of K1 leave in zbuf (0 with rng_ahead: all of them)
+    devmem::Owner<> mem;             // every buffer above is this owner's: `delete` gives them back (last member: the offsets above stay put)
 };
 
 static const int CENTER_SLOTS = 64;           // shards a group can gather the centre of its cloud over (sharded.hpp MAX_SHARDS)
@@ -144,6 +147,7 @@ struct smcmi_handle {
     smcmi_lik_device_fn dcb[2] = {nullptr, nullptr};
     void *dcb_ud[2] = {nullptr, nullptr};
     DevCallbackBuffers *dcbuf = nullptr;
+    devmem::Owner<> mem;           // every device / pinned buffer above is this owner's (devmem.hpp); e2, cbuf and dcbuf hold their own
 };
 // is likelihood `which` of the handle a user closure - a host callback or a device callback?  (which = 0: "this is a closure run")
 static inline bool closure_lik(const smcmi_handle *h, int which = 0) { return h->cb[which] != nullptr || h->dcb[which] != nullptr; }

@@ -23,7 +23,7 @@ static int mbox_alloc(smcmi_handle *h) {
     HIP_TRY(hipSetDevice(h->cfg.device));
     // fine-grained: stores from a peer GPU and this GPU's polling loads meet in memory, not in a die's L2
     const size_t words = (size_t)MB_ALLOC_WORDS + mbox_sel_words(h);
-    HIP_TRY(hipExtMallocWithFlags((void **)&h->d_mbox, sizeof(unsigned long long) * words, hipDeviceMallocFinegrained));
+    HIP_TRY(h->mem.alloc(&h->d_mbox, words, devmem::Kind::FineGrained));
     HIP_TRY(hipMemset(h->d_mbox, 0xFF, sizeof(unsigned long long) * words));
     if (int e = mbox_reset_flag(h, nullptr)) return e;
     HIP_TRY(hipDeviceSynchronize());              // (null-stream fill: not ordered with the handle's non-blocking stream)
@@ -31,8 +31,8 @@ static int mbox_alloc(smcmi_handle *h) {
 }
 static int mbox_set_peers(smcmi_handle *h, const std::vector<unsigned long long *> &peers) {
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (h->d_peers) { hipFree(h->d_peers); h->d_peers = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_peers, sizeof(unsigned long long *) * peers.size()));
+    h->mem.release(&h->d_peers);
+    HIP_TRY(h->mem.alloc(&h->d_peers, peers.size()));
     HIP_TRY(hipMemcpy(h->d_peers, peers.data(), sizeof(unsigned long long *) * peers.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
     h->h_peers = peers;
@@ -106,14 +106,14 @@ static int mbox_import(smcmi_handle *h, int world, int rank, const uint8_t *all)
 static int mbox_selftest(smcmi_handle *h, int world, int rank, int rounds, int *errs_out) {
     if (!h->d_peers || (int)h->h_peers.size() != world) return set_err(SMCMI_ERR_STATE, "mailbox: peers not imported");
     HIP_TRY(hipSetDevice(h->cfg.device));
+    devmem::Owner<> tmp;                    // (d_err: gone on every return)
     int *d_err = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_err, sizeof(int)));
+    HIP_TRY(tmp.alloc(&d_err, 1));
     HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int), h->stream));
     k_mbox_selftest<<<1, 128, 0, h->stream>>>(h->d_peers, h->d_mbox, world, rank, rounds, d_err);
     int e = 0;
     HIP_TRY(hipMemcpyAsync(&e, d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    hipFree(d_err);
     *errs_out = e;
     return 0;
 }
@@ -129,18 +129,16 @@ static int mbox_setup_remote(ShardGroup &g) {
     const int world = h->world, rank = h->rank;
     uint8_t mine[64] = {0};
     double fail = mbox_export(h, mine) ? 1.0 : 0.0;
+    devmem::Owner<> tmp;                    // (d_send, d_recv: gone on every return)
     double *d_send = nullptr, *d_recv = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_send, 64));
-    HIP_TRY(hipMalloc((void **)&d_recv, 64 * (size_t)world));
+    HIP_TRY(tmp.alloc(&d_send, 8));
+    HIP_TRY(tmp.alloc(&d_recv, 8 * (size_t)world));
     HIP_TRY(hipMemcpyAsync(d_send, mine, 64, hipMemcpyHostToDevice, h->stream));
-    if (int e = g.allgather([=](smcmi_handle *) { return (const double *)d_send; }, [=](smcmi_handle *) { return d_recv; }, (size_t)8)) {   // 64 bytes = 8 doubles per rank
-        hipFree(d_send); hipFree(d_recv);
-        return e;
-    }
+    if (int e = g.allgather([=](smcmi_handle *) { return (const double *)d_send; }, [=](smcmi_handle *) { return d_recv; }, (size_t)8)) return e;   // 64 bytes = 8 doubles per rank
     std::vector<uint8_t> all(64 * (size_t)world);
     HIP_TRY(hipMemcpyAsync(all.data(), d_recv, all.size(), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    hipFree(d_send); hipFree(d_recv);
+    tmp.release_all();
     if (fail == 0.0 && mbox_import(h, world, rank, all.data())) fail = 1.0;
     auto agree = [&](double mine_bad, double *total) -> int {           // sum of the ranks' failure counts
         HIP_TRY(hipMemcpyAsync(h->d_comm, &mine_bad, sizeof(double), hipMemcpyHostToDevice, h->stream));

@@ -99,7 +99,7 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
     // the run is void) may have left late arrivals behind - in stream order they precede this fill
     HIP_TRY(hipMemsetAsync(h->d_prep_tick, 0, 8 * sizeof(double), h->stream));
     if (!cont) { if (int e = first_records(h, rc)) return e; }
-    if (sw().prof2.set && !h->d_prof) { if (dmalloc(&h->d_prof, 32)) return SMCMI_ERR_HIP; }
+    if (sw().prof2.set && !h->d_prof) { if (dmalloc(h->mem, &h->d_prof, 32)) return SMCMI_ERR_HIP; }
     if (int e = ensure_zbuf(h, rc->n_mh_steps, rc->n_blocks)) return e;
     const int solver_passes = rc->solver_passes >= 1 ? rc->solver_passes : DEFAULT_SOLVER_PASSES;
     const int first_passes = std::max(solver_passes, FIRST_SOLVER_PASSES);
@@ -128,11 +128,10 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
     const int run_ahead = 1;      // (config 4: 30.6 ms at 1, 30.8 at 2, 31.1 at 4 - fewer idle launches behind a stall; measured in round 4, the switch retired in round 6)
     bool fixed_ns = !adaptive && can_fuse_cm(h) && sel_mode != 1 && sw().fixed_no_select != 0;        // (development: SMCMI_FIXED_NO_SELECT=0 = the seven-launch stage)
     if (fixed_ns && !h->h_note) {
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            h->h_note = (volatile int *)hp; h->d_note = (int *)dp;
+        int *hp = nullptr, *dp = nullptr;
+        if (h->mem.alloc(&hp, 16, devmem::Kind::Mapped, &dp) == hipSuccess) {
+            h->h_note = hp; h->d_note = dp;
         } else {
-            if (hp) hipHostFree(hp);
             (void)hipGetLastError();
             fixed_ns = false;
         }

@@ -15,16 +15,6 @@
 
 
 constexpr int SEG3_MAX_LAUNCHES = 4096;     // segment launches of one run whose stage counts are kept for the profile (more are not timed)
-static void free_eng2(Eng2 *e) {
-    if (!e) return;
-    void *ptrs[] = {e->d_ctl, e->rows_mut, e->rows_cm, e->csum, e->csum_full, e->rows_gm, e->rows_pass[0], e->rows_pass[1], e->vt_mut, e->vt_cm,
-                    e->vt_gm, e->vt_pass, e->d_ranges, e->d_ranges_all, e->d_prof, e->d_pre, e->d_tick, e->d_tick3, e->d_rec3, e->d_to3, e->d_done3, e->d_gran3, e->d_sel3, e->d_transit3};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    if (e->h_note3) hipHostFree(e->h_note3);
-    delete e;
-}
-
 // The plan (route.hpp) of handle h as shard `rank` of a run of `world` shards, `n_handles` of them in this process.  group_call: the run came
 // through smcmi_run_sharded / smcmi_run_group - it only picks the driver of a run engine 2 does not serve.
 static int handle_plan(const smcmi_handle *h, int world, int rank, int n_handles, bool rccl, bool group_call, const smcmi_run_config *rc, RunPlan *out) {
@@ -40,33 +30,29 @@ static int ensure_eng2(smcmi_handle *h, int world, const RunPlan &p) {
     if (!p.geo_ok) return set_err(SMCMI_ERR_UNSUPPORTED, "engine 2: unsupported shard geometry");
     const Geo2 &g = p.geo;
     if (h->e2 && h->e2->world == world && h->e2->g.direct == g.direct && h->e2->g.inker == g.inker && h->e2->g.nb2 == g.nb2 && h->e2->g.v0 == g.v0 && h->e2->g.t2 == g.t2 && h->e2->g.nb1 == g.nb1 && h->e2->g.wide == g.wide && h->e2->g.V == g.V && h->e2->g.nv == g.nv) return 0;
-    if (h->e2) { free_eng2(h->e2); h->e2 = nullptr; }
-    Eng2 *e = new Eng2();
+    delete h->e2;
+    h->e2 = nullptr;
+    // (built aside and installed only when complete: a failure below, the fills included, destroys it with everything it has allocated)
+    std::unique_ptr<Eng2> e(new Eng2());
+    e->mem.poison = sw().poison_alloc;
     e->g = g; e->world = world;
     const int npf = pad2(h->npairs + 2), npp = pad2(h->npairs);
     const size_t n1 = (size_t)g.Vl * g.nb1, n2 = (size_t)g.Vl * g.nb2, ng = (size_t)g.Vl * g.nbg;
-    if (dmalloc(&e->d_ctl, 1) || dmalloc(&e->rows_mut, n2 * RMUT) || dmalloc(&e->rows_cm, n1 * npf) || dmalloc(&e->csum, n1) ||
-        dmalloc(&e->csum_full, (size_t)g.V * g.nb1) || dmalloc(&e->rows_gm, ng * npp) || dmalloc(&e->rows_pass[0], n1 * 2 * KC) ||
-        dmalloc(&e->rows_pass[1], n1 * 2 * KC) || dmalloc(&e->vt_mut, (size_t)g.V * RMUT) || dmalloc(&e->vt_cm, (size_t)g.V * npf) ||
-        dmalloc(&e->vt_gm, (size_t)g.V * npp) || dmalloc(&e->vt_pass, (size_t)g.V * 2 * KC) || dmalloc(&e->d_ranges, 2 * V2_MAXV + 2) || dmalloc(&e->d_ranges_all, (size_t)V2_MAXV * (2 * V2_MAXV + 2)) || dmalloc(&e->d_pre, 1) || dmalloc(&e->d_tick, 2 * V2_MAXV * TICK2_STRIDE)) {
-        free_eng2(e);
+    if (dmalloc(e->mem, &e->d_ctl, 1) || dmalloc(e->mem, &e->rows_mut, n2 * RMUT) || dmalloc(e->mem, &e->rows_cm, n1 * npf) || dmalloc(e->mem, &e->csum, n1) ||
+        dmalloc(e->mem, &e->csum_full, (size_t)g.V * g.nb1) || dmalloc(e->mem, &e->rows_gm, ng * npp) || dmalloc(e->mem, &e->rows_pass[0], n1 * 2 * KC) ||
+        dmalloc(e->mem, &e->rows_pass[1], n1 * 2 * KC) || dmalloc(e->mem, &e->vt_mut, (size_t)g.V * RMUT) || dmalloc(e->mem, &e->vt_cm, (size_t)g.V * npf) ||
+        dmalloc(e->mem, &e->vt_gm, (size_t)g.V * npp) || dmalloc(e->mem, &e->vt_pass, (size_t)g.V * 2 * KC) || dmalloc(e->mem, &e->d_ranges, 2 * V2_MAXV + 2) || dmalloc(e->mem, &e->d_ranges_all, (size_t)V2_MAXV * (2 * V2_MAXV + 2)) || dmalloc(e->mem, &e->d_pre, 1) || dmalloc(e->mem, &e->d_tick, 2 * V2_MAXV * TICK2_STRIDE))
         return SMCMI_ERR_HIP;
-    }
     if (g.direct || (g.inker && !g.wide && g.t2 == T3 && g.nb1 == g.nb2)) {       // engine 3 (stage3.hpp) can serve this geometry: tickets, records, time-out words, per-launch stage counts
         const size_t gw = k3_table_words(g.Vl * g.nb2);
-        if (dmalloc(&e->d_tick3, 2 * SEG3_TICKS) || dmalloc(&e->d_rec3, REC3_WORDS) || dmalloc(&e->d_to3, 2) || dmalloc(&e->d_done3, SEG3_MAX_LAUNCHES) ||
-            dmalloc(&e->d_gran3, gw) || dmalloc(&e->d_sel3, 1)) {
-            free_eng2(e);
+        if (dmalloc(e->mem, &e->d_tick3, 2 * SEG3_TICKS) || dmalloc(e->mem, &e->d_rec3, REC3_WORDS) || dmalloc(e->mem, &e->d_to3, 2) || dmalloc(e->mem, &e->d_done3, SEG3_MAX_LAUNCHES) ||
+            dmalloc(e->mem, &e->d_gran3, gw) || dmalloc(e->mem, &e->d_sel3, 1))
             return SMCMI_ERR_HIP;
-        }
         // (the exit note of a segment: host-mapped; without it the host copies Ctl2 and syncs as for every other launch)
-        if (hipHostMalloc(&e->h_note3, 64 + sizeof(Ctl2), hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&e->d_note3, e->h_note3, 0) == hipSuccess) {
-            memset(e->h_note3, 0, 64 + sizeof(Ctl2));
-        } else {
-            if (e->h_note3) hipHostFree(e->h_note3);
-            e->h_note3 = e->d_note3 = nullptr;
-            (void)hipGetLastError();
-        }
+        char *hp = nullptr, *dp = nullptr;
+        if (e->mem.alloc(&hp, 64 + sizeof(Ctl2), devmem::Kind::Mapped, &dp) == hipSuccess) memset(hp, 0, 64 + sizeof(Ctl2));
+        else (void)hipGetLastError();
+        e->h_note3 = hp; e->d_note3 = dp;
         HIP_TRY(hipMemsetAsync(e->d_tick3, 0, 2 * SEG3_TICKS * sizeof(int), h->stream));
         HIP_TRY(hipMemsetAsync(e->d_rec3, 0xFF, REC3_WORDS * sizeof(unsigned long long), h->stream));
         HIP_TRY(hipMemsetAsync(e->d_gran3, 0xFF, gw * sizeof(unsigned long long), h->stream));
@@ -79,7 +65,7 @@ static int ensure_eng2(smcmi_handle *h, int world, const RunPlan &p) {
     HIP_TRY(hipMemsetAsync(e->rows_gm, 0, ng * npp * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(e->csum, 0, n1 * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(e->csum_full, 0, (size_t)g.V * g.nb1 * sizeof(double), h->stream));
-    h->e2 = e;
+    h->e2 = e.release();
     return 0;
 }
 
@@ -119,8 +105,9 @@ static int seg3_ready(smcmi_handle *h, const RunPlan &p, bool *ok) {
     if (e->seg_ch != ch) { e->seg_ch = ch; if (e->e3_state > 0) e->e3_state = 0; }      // (another grid: the residency self-test again)
     if (e->e3_state < 0) return 0;
     if (e->e3_state == 0) {
+        devmem::Owner<> tmp;                // (d_ok: gone on every return)
         int *d_ok = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_ok, sizeof(int)));
+        HIP_TRY(tmp.alloc(&d_ok, 1));
         HIP_TRY(hipMemsetAsync(d_ok, 0, sizeof(int), h->stream));
         if (int rc = seg3_time_out_words(h, 50.0)) return rc;
         const size_t lds = 96 * 1024;                       // more than half a CU's LDS: one block per CU, the placement the segment kernel must survive
@@ -131,7 +118,6 @@ static int seg3_ready(smcmi_handle *h, const RunPlan &p, bool *ok) {
         HIP_TRY(hipMemcpyAsync(&okc, d_ok, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(fl, e->d_to3, sizeof(fl), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        hipFree(d_ok);
         e->e3_state = (okc == grid && fl[0] == 0) ? 1 : -1;
         HIP_TRY(hipMemsetAsync(e->d_tick3, 0, 2 * SEG3_TICKS * sizeof(int), h->stream));
         if (sw().trace) fprintf(stderr, "[smcmi3] residency self-test: %d of %d blocks, time-out flag %llu -> engine 3 %s\n", okc, grid, fl[0], e->e3_state > 0 ? "on" : "off");
@@ -194,7 +180,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     }
     if (sw().prof2.set && !h0->e2->d_prof) {
         // (the buffer's layout: stage2.hpp PROF2_*)
-        if (dmalloc(&h0->e2->d_prof, PROF2_WORDS)) return SMCMI_ERR_HIP;
+        if (dmalloc(h0->e2->mem, &h0->e2->d_prof, PROF2_WORDS)) return SMCMI_ERR_HIP;
         HIP_TRY(hipMemset(h0->e2->d_prof, 0, PROF2_WORDS * sizeof(long long)));
         HIP_TRY(hipDeviceSynchronize());
         h0->e2->prof_stage = sw().prof2.v;
@@ -348,7 +334,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         sl = Sel3Args{};
         sl.method = rc->resampling_method; sl.cum = h0->d_cum; sl.anc = h0->d_anc;
         if (k3_sel_cols(d, rc->alpha == 1.0) == 0 || e->seg_ch == 2) {      // (mixture proposals beyond n_para 7: the particle in transit does not fit the kernel's LDS; two chunks: the one in registers)
-            if (!e->d_transit3 && dmalloc(&e->d_transit3, nblk * (size_t)(d + 5) * T3)) return SMCMI_ERR_HIP;
+            if (!e->d_transit3 && dmalloc(e->mem, &e->d_transit3, nblk * (size_t)(d + 5) * T3)) return SMCMI_ERR_HIP;
             sl.transit = e->d_transit3;
         }
         sl.g_sel = e->d_gran3 + nblk * (72 + RMUT) * 2 + (size_t)V2_MAXV * (72 + RMUT) * 2; sl.gt_sel = sl.g_sel + nblk * 2 * 2;

@@ -315,17 +315,17 @@ struct ShardGroup {
 static int ensure_shard_buffers(smcmi_handle *h) {
     const long long N = h->cfg.n_parts;
     if (!h->d_tot_ess) {
-        if (dmalloc(&h->d_tot_ess, 2 * KC) || dmalloc(&h->d_tot_fin, 2) || dmalloc(&h->d_tot_mom, h->npairs + 2) || dmalloc(&h->d_tot_acc, ES + MAX_SHARDS))
+        if (dmalloc(h->mem, &h->d_tot_ess, 2 * KC) || dmalloc(h->mem, &h->d_tot_fin, 2) || dmalloc(h->mem, &h->d_tot_mom, h->npairs + 2) || dmalloc(h->mem, &h->d_tot_acc, ES + MAX_SHARDS))
             return SMCMI_ERR_HIP;
         HIP_TRY(hipMemsetAsync(h->d_tot_acc, 0, sizeof(double) * (ES + MAX_SHARDS), h->stream));   // (the handle's stream is non-blocking: keep its work on it)
     }
     if (!h->d_cum_full) {
-        if (dmalloc(&h->d_cum_full, N)) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_cum_full, N)) return SMCMI_ERR_HIP;
         h->nb_full = (int)std::min<long long>(1024, std::max<long long>(1, (N + 511) / 512));
-        if (dmalloc(&h->d_part_full, (size_t)h->nb_full * 2) || dmalloc(&h->d_off_full, h->nb_full)) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_part_full, (size_t)h->nb_full * 2) || dmalloc(h->mem, &h->d_off_full, h->nb_full)) return SMCMI_ERR_HIP;
     }
     if (!h->d_full_w) {
-        if (dmalloc(&h->d_full_w, N) || dmalloc(&h->d_full_cloud, (size_t)N * h->R)) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_full_w, N) || dmalloc(h->mem, &h->d_full_cloud, (size_t)N * h->R)) return SMCMI_ERR_HIP;
     }
     return 0;
 }
@@ -428,7 +428,8 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     // skip_begin: resume of such a stage through the certificate path
     // use_graph == 2: HIP events around the first local shard's mutation launches (the `roofline` figure of a multi-GPU bench line)
     const bool profile = rc->use_graph == 2;
-    std::vector<hipEvent_t> mut_evs;
+    devmem::Handles prof_evs;              // (destroyed on every return)
+    std::vector<hipEvent_t> &mut_evs = prof_evs.events;
     auto enqueue = [&](int p0, int P, int mode, bool spec = false, bool skip_begin = false) -> int {
         if (spec) P = 0;
         const int fin_slot = P == 0 ? 0 : (P & 1);
@@ -482,7 +483,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
                 HIP_TRY(hipSetDevice(h->cfg.device));
                 launch_prepare_in_run(h, h->d_tot_mom, 1, 3, fin_slot);
                 hipEvent_t pe0 = nullptr, pe1 = nullptr;
-                if (profile && h == h0) { hipEventCreate(&pe0); hipEventCreate(&pe1); mut_evs.push_back(pe0); mut_evs.push_back(pe1); hipEventRecord(pe0, h->stream); }
+                if (profile && h == h0) { prof_evs.event(&pe0); prof_evs.event(&pe1); hipEventRecord(pe0, h->stream); }
                 const int nbl = launch_mutate(h, rc->n_blocks, 0, rc->alpha);
                 if (pe1) hipEventRecord(pe1, h->stream);
                 if (predict) k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_esum_part, nbl, ES, h->d_tot_acc, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
@@ -614,7 +615,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             HIP_TRY(hipSetDevice(h->cfg.device));
             launch_prepare_in_run(h, h->d_tot_mom, 1, 2);
             hipEvent_t pe0 = nullptr, pe1 = nullptr;
-            if (profile && h == h0) { hipEventCreate(&pe0); hipEventCreate(&pe1); mut_evs.push_back(pe0); mut_evs.push_back(pe1); hipEventRecord(pe0, h->stream); }
+            if (profile && h == h0) { prof_evs.event(&pe0); prof_evs.event(&pe1); hipEventRecord(pe0, h->stream); }
             const int nbl = launch_mutate(h, rc->n_blocks, 0, rc->alpha);
             if (pe1) hipEventRecord(pe1, h->stream);
             if (predict) k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_esum_part, nbl, ES, h->d_tot_acc, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
@@ -725,7 +726,6 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, mut_evs[k], mut_evs[k + 1]) == hipSuccess) { res->kernel_ms_mutate += std::max(0.0, (double)ms - over); res->n_mutate_launches += 1; }
         }
-        for (hipEvent_t e : mut_evs) hipEventDestroy(e);
     }
     return finish_error(s);
 }

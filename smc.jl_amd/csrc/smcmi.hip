@@ -10,10 +10,6 @@
 #include "switches.hpp"
 #include "route.hpp"
 
-static void free_eng2(Eng2 *e);
-static void free_callback_buffers(CallbackBuffers *b);
-static void free_dev_callback_buffers(DevCallbackBuffers *b);
-
 static thread_local std::string g_err;
 extern "C" const char *smcmi_last_error(void) { return g_err.c_str(); }
 extern "C" int smcmi_version(void) { return 1; }
@@ -107,19 +103,10 @@ static int push_model(smcmi_handle *h) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
+// `count` elements of plain device memory that `o` owns from here on (devmem.hpp: SMCMI_POISON_ALLOC fills and reports them there)
 template <class T>
-static int dmalloc(T **p, size_t count) {
-    HIP_TRY(hipMalloc((void **)p, (count ? count : 1) * sizeof(T)));
-    // development (SMCMI_POISON_ALLOC=1): fresh device memory reads as NaN / -1, so a read of something never written shows up
-    // in every test instead of depending on what the allocator hands back
-    const int poison = sw().poison_alloc;
-    static int counter = 0;
-    const int idx = counter++;
-    if (poison) {
-        HIP_TRY(hipMemset(*p, 0xFF, (count ? count : 1) * sizeof(T)));
-        HIP_TRY(hipDeviceSynchronize());        // (the fill runs on the null stream: it must not land after the handle's first copies)
-        if (poison > 1) fprintf(stderr, "[smcmi] poisoned allocation #%d (%zu bytes)\n", idx, (count ? count : 1) * sizeof(T));
-    }
+static int dmalloc(devmem::Owner<> &o, T **p, size_t count) {
+    HIP_TRY(o.alloc(p, count));
     return 0;
 }
 static int err_from_state(int code) {
@@ -182,7 +169,7 @@ static int nan_ess_error_from_cloud(smcmi_handle *h, double phi_n, double phi_pr
 }
 
 static int set_mutate_attrs(smcmi_handle *h);
-static void smcmi_comm_release(smcmi_handle *h);
+static int create_impl(smcmi_handle *h, const smcmi_config *cfg);
 
 // ------------------------------------------------------------------------------------------------ lifetime
 extern "C" int smcmi_create(const smcmi_config *cfg, smcmi_handle **out) {
@@ -195,7 +182,18 @@ extern "C" int smcmi_create(const smcmi_config *cfg, smcmi_handle **out) {
         return set_err(SMCMI_ERR_HIP, "no HIP device available: libsmcmi has no CPU fallback (hipGetDeviceCount failed)");
     if (cfg->device < 0 || cfg->device >= ndev) return set_err(SMCMI_ERR_ARG, "bad device ordinal");
     HIP_TRY(hipSetDevice(cfg->device));
+    // one exit: whatever step of the set-up fails, the handle goes with its stream and everything it has allocated, *out stays as it was
     smcmi_handle *h = new smcmi_handle();
+    if (const int rc = create_impl(h, cfg)) {
+        smcmi_destroy(h);
+        (void)hipGetLastError();          // (the failure has been reported: it must not turn up behind a later launch)
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+static int create_impl(smcmi_handle *h, const smcmi_config *cfg) {
+    h->mem.poison = sw().poison_alloc;
     h->cfg = *cfg;
     if (h->cfg.n_local <= 0) h->cfg.n_local = cfg->n_parts;
     if (h->cfg.max_stages < 2) h->cfg.max_stages = 2;
@@ -206,15 +204,15 @@ extern "C" int smcmi_create(const smcmi_config *cfg, smcmi_handle **out) {
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     const long long n = h->n;
     for (int b = 0; b < 2; ++b) {
-        if (dmalloc(&h->cl.buf[b], (size_t)n * h->R)) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->cl.buf[b], (size_t)n * h->R)) return SMCMI_ERR_HIP;
         HIP_TRY(hipMemsetAsync(h->cl.buf[b], 0, (size_t)n * h->R * sizeof(double), h->stream));
     }
     h->cl.n = n;
     h->cl.R = h->R;
-    if (dmalloc(&h->d_st, 1) || dmalloc(&h->d_model, 1)) return SMCMI_ERR_HIP;
+    if (dmalloc(h->mem, &h->d_st, 1) || dmalloc(h->mem, &h->d_model, 1)) return SMCMI_ERR_HIP;
     const int ms = h->cfg.max_stages;
-    if (dmalloc(&h->rec.phi, ms) || dmalloc(&h->rec.ess, ms) || dmalloc(&h->rec.c, ms) || dmalloc(&h->rec.accept, ms) ||
-        dmalloc(&h->rec.resampled, ms))
+    if (dmalloc(h->mem, &h->rec.phi, ms) || dmalloc(h->mem, &h->rec.ess, ms) || dmalloc(h->mem, &h->rec.c, ms) || dmalloc(h->mem, &h->rec.accept, ms) ||
+        dmalloc(h->mem, &h->rec.resampled, ms))
         return SMCMI_ERR_HIP;
     h->nb_e = (int)std::min<long long>(512, std::max<long long>(1, (n + 511) / 512));      // (512 rows, not 1024: less for the prepare launch to total - measured 2-4 % per run from 4e5 to 1e7 particles)
     h->nb_m = (int)std::min<long long>(256, std::max<long long>(1, (n + MT - 1) / MT));
@@ -236,18 +234,18 @@ extern "C" int smcmi_create(const smcmi_config *cfg, smcmi_handle **out) {
     h->mom_lds = (size_t)((h->d + 2) * (MT + 1)) * sizeof(double) + 2 * (size_t)h->npairs + 16;
     h->comm_cap = std::max<long long>(2 * KC, h->npairs) + 8;
     h->prep_lds = (size_t)(((h->npairs + 63) / 64) * 64 + 4 * h->d * h->d + 8) * sizeof(double);
-    if (dmalloc(&h->d_part_ess[0], (size_t)h->nb_e * 2 * KC) || dmalloc(&h->d_part_ess[1], (size_t)h->nb_e * 2 * KC) || dmalloc(&h->d_part_fin, (size_t)h->nb_e * 2) || dmalloc(&h->d_part_cm, (size_t)h->nb_e * (h->npairs + 2)) || dmalloc(&h->d_prep_rows, (size_t)PREP_G * PT + 8) || dmalloc(&h->d_wt, n) ||
-        dmalloc(&h->d_chunk_off, h->nb_e) || dmalloc(&h->d_cum, n) || dmalloc(&h->d_anc, n) ||
-        dmalloc(&h->d_part_mom, (size_t)std::max(h->nb_m, h->nb_mr) * h->npairs) || dmalloc(&h->d_totals, h->npairs) ||
-        dmalloc(&h->d_acc_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(&h->d_esum_part, (size_t)std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4}) * ES) || dmalloc(&h->d_esum_red, (size_t)ESUM_RED_ROWS * (ES + 1)) || dmalloc(&h->d_emax_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(&h->d_comm, h->comm_cap) || dmalloc(&h->d_offsets, n) ||
-        dmalloc(&h->d_center, (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * h->nb_c + 1)) ||
-        dmalloc(&h->d_flag, 4) || dmalloc(&h->d_mix, (size_t)10 * (3 * 100 + 22)) || dmalloc(&h->d_mixpos, 100))
+    if (dmalloc(h->mem, &h->d_part_ess[0], (size_t)h->nb_e * 2 * KC) || dmalloc(h->mem, &h->d_part_ess[1], (size_t)h->nb_e * 2 * KC) || dmalloc(h->mem, &h->d_part_fin, (size_t)h->nb_e * 2) || dmalloc(h->mem, &h->d_part_cm, (size_t)h->nb_e * (h->npairs + 2)) || dmalloc(h->mem, &h->d_prep_rows, (size_t)PREP_G * PT + 8) || dmalloc(h->mem, &h->d_wt, n) ||
+        dmalloc(h->mem, &h->d_chunk_off, h->nb_e) || dmalloc(h->mem, &h->d_cum, n) || dmalloc(h->mem, &h->d_anc, n) ||
+        dmalloc(h->mem, &h->d_part_mom, (size_t)std::max(h->nb_m, h->nb_mr) * h->npairs) || dmalloc(h->mem, &h->d_totals, h->npairs) ||
+        dmalloc(h->mem, &h->d_acc_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(h->mem, &h->d_esum_part, (size_t)std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4}) * ES) || dmalloc(h->mem, &h->d_esum_red, (size_t)ESUM_RED_ROWS * (ES + 1)) || dmalloc(h->mem, &h->d_emax_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(h->mem, &h->d_comm, h->comm_cap) || dmalloc(h->mem, &h->d_offsets, n) ||
+        dmalloc(h->mem, &h->d_center, (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * h->nb_c + 1)) ||
+        dmalloc(h->mem, &h->d_flag, 4) || dmalloc(h->mem, &h->d_mix, (size_t)10 * (3 * 100 + 22)) || dmalloc(h->mem, &h->d_mixpos, 100))
         return SMCMI_ERR_HIP;
     h->d_prep_tick = reinterpret_cast<int *>(h->d_prep_rows + (size_t)PREP_G * PT);
     HIP_TRY(hipMemset(h->d_center + (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * h->nb_c), 0, sizeof(double)));      // k_center_one's ticket
     HIP_TRY(hipMemset(h->d_prep_tick, 0, 8 * sizeof(double)));
     if (h->cfg.store_history) {
-        if (dmalloc(&h->d_hist_w, (size_t)n * ms) || dmalloc(&h->d_hist_W, (size_t)n * ms)) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_hist_w, (size_t)n * ms) || dmalloc(h->mem, &h->d_hist_W, (size_t)n * ms)) return SMCMI_ERR_HIP;
     }
     memset(&h->h_st, 0, sizeof(DevState));
     h->h_st.rp.n_parts = cfg->n_parts;
@@ -269,33 +267,6 @@ extern "C" int smcmi_create(const smcmi_config *cfg, smcmi_handle **out) {
     HIP_TRY(hipFuncSetAttribute((const void *)k_mutate<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mut_lds));
     HIP_TRY(hipFuncSetAttribute((const void *)k_mutate<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mut_lds));
     if (set_mutate_attrs(h)) return SMCMI_ERR_HIP;
-    *out = h;
-    return 0;
-}
-
-extern "C" int smcmi_destroy(smcmi_handle *h) {
-    if (!h) return 0;
-    hipSetDevice(h->cfg.device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->nccl) smcmi_comm_release(h);
-    if (h->e2) { free_eng2(h->e2); h->e2 = nullptr; }
-    for (void *p : h->ipc_opened) hipIpcCloseMemHandle(p);
-    h->ipc_opened.clear();
-    if (h->d_mbox) { hipFree(h->d_mbox); h->d_mbox = nullptr; }
-    if (h->d_peers) { hipFree(h->d_peers); h->d_peers = nullptr; }
-    if (h->cbuf) { free_callback_buffers(h->cbuf); h->cbuf = nullptr; }
-    if (h->dcbuf) { free_dev_callback_buffers(h->dcbuf); h->dcbuf = nullptr; }
-    if (h->h_note) { hipHostFree((void *)h->h_note); h->h_note = nullptr; h->d_note = nullptr; }
-    void *ptrs[] = {h->cl.buf[0], h->cl.buf[1], h->d_st, h->d_model, h->d_data[0], h->d_data[1], h->d_aux[0], h->d_aux[1],
-                    h->rec.phi, h->rec.ess, h->rec.c, h->rec.accept, h->rec.resampled, h->d_sched, h->d_part_ess[0], h->d_part_ess[1],
-                    h->d_part_fin, h->d_part_cm, h->d_prep_rows, h->d_wt, h->d_chunk_off, h->d_cum, h->d_anc, h->d_part_mom, h->d_totals, h->d_acc_part, h->d_esum_part, h->d_esum_red, h->d_emax_part, h->d_zbuf,
-                    h->d_comm, h->d_offsets, h->d_hist_w, h->d_hist_W, h->d_prop, h->d_prop_lp, h->d_prop_q,
-                    h->d_lik_new, h->d_lik_old, h->d_acc_count, h->d_flag, h->d_cum_full, h->d_part_full, h->d_off_full,
-                    h->d_tot_ess, h->d_tot_fin, h->d_tot_mom, h->d_tot_acc, h->d_full_w, h->d_full_cloud, h->d_prof, h->d_mix, h->d_mixpos, h->d_snap, h->d_center};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
     return 0;
 }
 
@@ -345,8 +316,8 @@ extern "C" int smcmi_set_likelihood(smcmi_handle *h, int32_t which, int32_t fami
     if (n_par > LIK_PAR_MAX) return set_err(SMCMI_ERR_ARG, "too many likelihood parameters");
     HIP_TRY(hipSetDevice(h->cfg.device));
     LikDev &l = h->h_model.lik[which];
-    if (h->d_data[which]) { hipFree(h->d_data[which]); h->d_data[which] = nullptr; }
-    if (h->d_aux[which]) { hipFree(h->d_aux[which]); h->d_aux[which] = nullptr; }
+    h->mem.release(&h->d_data[which]);
+    h->mem.release(&h->d_aux[which]);
     memset(&l, 0, sizeof(LikDev));
     l.family = family;
     h->cb[which] = nullptr; h->cb_ud[which] = nullptr;            // a device family (or none) replaces a registered host callback
@@ -370,7 +341,7 @@ extern "C" int smcmi_set_likelihood(smcmi_handle *h, int32_t which, int32_t fami
         return set_err(SMCMI_ERR_ARG, "3-equation families need data 3 x T, regressors with >= T columns, d = 9");
     l.c0 = lik_const_host(family, l.par, d);
     if (data && rows * cols > 0) {
-        if (dmalloc(&h->d_data[which], (size_t)(rows * cols))) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_data[which], (size_t)(rows * cols))) return SMCMI_ERR_HIP;
         HIP_TRY(hipMemcpy(h->d_data[which], data, sizeof(double) * rows * cols, hipMemcpyHostToDevice));
     }
     if (family == SMCMI_LIK_LGSS_KALMAN) {
@@ -382,11 +353,11 @@ extern "C" int smcmi_set_likelihood(smcmi_handle *h, int32_t which, int32_t fami
         for (int i = 0; i < 8; ++i)
             for (int j = i; j < 8; ++j)
                 for (int m = 0; m < 3; ++m) ext[KALMAN_AUX_RR + ksym(i, j) * 3 + m] = Rm[i * 3 + m] * Rm[j * 3 + m];
-        if (dmalloc(&h->d_aux[which], ext.size())) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_aux[which], ext.size())) return SMCMI_ERR_HIP;
         HIP_TRY(hipMemcpy(h->d_aux[which], ext.data(), sizeof(double) * ext.size(), hipMemcpyHostToDevice));
         aux_rows = 1; aux_cols = KALMAN_AUX_TOTAL;
     } else if (aux && aux_rows * aux_cols > 0) {
-        if (dmalloc(&h->d_aux[which], (size_t)(aux_rows * aux_cols))) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_aux[which], (size_t)(aux_rows * aux_cols))) return SMCMI_ERR_HIP;
         HIP_TRY(hipMemcpy(h->d_aux[which], aux, sizeof(double) * aux_rows * aux_cols, hipMemcpyHostToDevice));
     }
     l.data = h->d_data[which]; l.rows = rows; l.cols = cols;
@@ -496,8 +467,8 @@ extern "C" int smcmi_set_likelihood_callback(smcmi_handle *h, int32_t which, smc
     h->cb[which] = fn; h->cb_ud[which] = user_data;
     h->dcb[which] = nullptr; h->dcb_ud[which] = nullptr;          // a host callback (or none) replaces a registered device callback
     LikDev &l = h->h_model.lik[which];
-    if (h->d_data[which]) { hipFree(h->d_data[which]); h->d_data[which] = nullptr; }
-    if (h->d_aux[which]) { hipFree(h->d_aux[which]); h->d_aux[which] = nullptr; }
+    h->mem.release(&h->d_data[which]);
+    h->mem.release(&h->d_aux[which]);
     memset(&l, 0, sizeof(LikDev));
     l.family = fn ? SMCMI_LIK_HOST_CALLBACK : SMCMI_LIK_NONE;
     if (which == 0) h->have_lik = fn != nullptr;
@@ -511,8 +482,8 @@ extern "C" int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const
     h->dcb[which] = fn; h->dcb_ud[which] = fn ? lik->user_data : nullptr;
     h->cb[which] = nullptr; h->cb_ud[which] = nullptr;            // replaces a registered host callback or device family
     LikDev &l = h->h_model.lik[which];
-    if (h->d_data[which]) { hipFree(h->d_data[which]); h->d_data[which] = nullptr; }
-    if (h->d_aux[which]) { hipFree(h->d_aux[which]); h->d_aux[which] = nullptr; }
+    h->mem.release(&h->d_data[which]);
+    h->mem.release(&h->d_aux[which]);
     memset(&l, 0, sizeof(LikDev));
     l.family = fn ? SMCMI_LIK_HOST_CALLBACK : SMCMI_LIK_NONE;      // (to the kernels both kinds of closure are "not evaluated here")
     h->lik_host_data[which].clear(); h->lik_host_aux[which].clear();
@@ -535,12 +506,7 @@ extern "C" int smcmi_callback_stats(smcmi_handle *h, int64_t *calls, int64_t *ev
 
 // ------------------------------------------------------------------------------------------------ stage primitives
 static int upload_sched(smcmi_handle *h, const double *sched, int n_phi) {
-    if (h->sched_len < n_phi) {
-        if (h->d_sched) hipFree(h->d_sched);
-        h->d_sched = nullptr;
-        if (dmalloc(&h->d_sched, n_phi)) return SMCMI_ERR_HIP;
-        h->sched_len = n_phi;
-    }
+    HIP_TRY(h->mem.regrow(&h->d_sched, &h->sched_len, (size_t)n_phi));
     HIP_TRY(hipMemcpyAsync(h->d_sched, sched, sizeof(double) * n_phi, hipMemcpyHostToDevice, h->stream));
     return 0;
 }
@@ -676,14 +642,15 @@ extern "C" int smcmi_bridge_resample(smcmi_handle *dst, smcmi_handle *src, int32
     HIP_TRY(hipSetDevice(src->cfg.device));
     if (pull_state(src) || pull_state(dst)) return SMCMI_ERR_HIP;
     dst->center_stale = true;
+    devmem::Owner<> tmp;                   // (d_off, d_anc: gone on every return)
     double *d_off = nullptr;
     if (offsets) {
         const long long cnt = method == SMCMI_RESAMPLE_MULTINOMIAL ? n_out : 1;
-        HIP_TRY(hipMalloc(&d_off, sizeof(double) * cnt));
+        HIP_TRY(tmp.alloc(&d_off, (size_t)cnt));
         HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(double) * cnt, hipMemcpyHostToDevice, src->stream));
     }
     long long *d_anc = nullptr;
-    if (ancestors_out) HIP_TRY(hipMalloc(&d_anc, sizeof(long long) * n_out));
+    if (ancestors_out) HIP_TRY(tmp.alloc(&d_anc, (size_t)n_out));
     k_weight_chunk_sums<<<src->nb_e, TB, 0, src->stream>>>(src->cl, src->d_st, src->d_part_fin);
     k_chunk_offsets<<<1, 1, 0, src->stream>>>(src->d_st, src->d_part_fin, src->nb_e, src->d_chunk_off, 0.0, 1);
     k_scan_weights<<<src->nb_e, TB, 0, src->stream>>>(src->cl, src->d_st, src->d_chunk_off, src->d_cum, 1, src->nb_e);
@@ -692,8 +659,6 @@ extern "C" int smcmi_bridge_resample(smcmi_handle *dst, smcmi_handle *src, int32
                                                                             d_off, d_anc);
     if (ancestors_out) HIP_TRY(hipMemcpyAsync(ancestors_out, d_anc, sizeof(long long) * n_out, hipMemcpyDeviceToHost, src->stream));
     HIP_TRY(hipStreamSynchronize(src->stream));
-    if (d_off) hipFree(d_off);
-    if (d_anc) hipFree(d_anc);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -934,8 +899,8 @@ extern "C" int smcmi_mutate(smcmi_handle *h, const double *mu_free, const double
 static int ensure_split_buffers(smcmi_handle *h) {
     if (h->d_prop) return 0;
     const long long n = h->n;
-    if (dmalloc(&h->d_prop, (size_t)n * (h->d + 1)) || dmalloc(&h->d_prop_lp, n) || dmalloc(&h->d_prop_q, n) ||       // (+ 1: the chunk-major layout's log-prior column)
-        dmalloc(&h->d_lik_new, n) || dmalloc(&h->d_lik_old, n) || dmalloc(&h->d_acc_count, n))
+    if (dmalloc(h->mem, &h->d_prop, (size_t)n * (h->d + 1)) || dmalloc(h->mem, &h->d_prop_lp, n) || dmalloc(h->mem, &h->d_prop_q, n) ||       // (+ 1: the chunk-major layout's log-prior column)
+        dmalloc(h->mem, &h->d_lik_new, n) || dmalloc(h->mem, &h->d_lik_old, n) || dmalloc(h->mem, &h->d_acc_count, n))
         return SMCMI_ERR_HIP;
     return 0;
 }
@@ -987,10 +952,7 @@ extern "C" int smcmi_accept(smcmi_handle *h, const double *loglik_new, const dou
 // In-run proposal set-up: block 0 prepares the proposal, the other blocks draw the stage's random numbers ahead (RngAhead) when
 // the register mutation kernel will run and the buffer fits.  from_totals as in k_prepare_mutation.
 static int grow_zbuf(smcmi_handle *h, size_t need) {
-    if (need <= h->zbuf_cap) return 0;
-    if (h->d_zbuf) { hipFree(h->d_zbuf); h->d_zbuf = nullptr; h->zbuf_cap = 0; }
-    if (dmalloc(&h->d_zbuf, need)) return SMCMI_ERR_HIP;
-    h->zbuf_cap = need;
+    HIP_TRY(h->mem.regrow(&h->d_zbuf, &h->zbuf_cap, need));
     return 0;
 }
 static int ensure_zbuf(smcmi_handle *h, int n_mh_steps, int n_blocks) {
@@ -1190,9 +1152,9 @@ extern "C" int smcmi_shard_resample(smcmi_handle *h, const double *dev_full_weig
     HIP_TRY(hipSetDevice(h->cfg.device));
     const long long N = h->cfg.n_parts;
     if (!h->d_cum_full) {
-        if (dmalloc(&h->d_cum_full, N)) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_cum_full, N)) return SMCMI_ERR_HIP;
         h->nb_full = (int)std::min<long long>(1024, std::max<long long>(1, (N + 511) / 512));
-        if (dmalloc(&h->d_part_full, (size_t)h->nb_full * 2) || dmalloc(&h->d_off_full, h->nb_full)) return SMCMI_ERR_HIP;
+        if (dmalloc(h->mem, &h->d_part_full, (size_t)h->nb_full * 2) || dmalloc(h->mem, &h->d_off_full, h->nb_full)) return SMCMI_ERR_HIP;
     }
     CloudPtrs wcl{};                      // view the full weight vector as a 1-column "cloud"
     wcl.buf[0] = wcl.buf[1] = const_cast<double *>(dev_full_weights);
@@ -1254,7 +1216,7 @@ static int run2_guarded(ShardGroup &g, const smcmi_run_config *rc, smcmi_result 
         for (auto *h : g.hs) {
             const long long cloud_n = (long long)h->n * h->R;
             HIP_TRY(hipSetDevice(h->cfg.device));
-            if (!h->d_snap && dmalloc(&h->d_snap, (size_t)(cloud_n + state_n))) return SMCMI_ERR_HIP;
+            if (!h->d_snap && dmalloc(h->mem, &h->d_snap, (size_t)(cloud_n + state_n))) return SMCMI_ERR_HIP;
             // (both copies stay on the device, in stream order: no host round trip at the start of a run)
             launch_copy_f64(h->d_snap, h->cl.buf[0], cloud_n, h->stream);
             HIP_TRY(hipMemcpyAsync(h->d_snap + cloud_n, h->d_st, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream));
@@ -1340,9 +1302,10 @@ extern "C" int smcmi_debug_proposal_densities(const double *para_draw, const dou
     if (d < 1 || d > 16) return set_err(SMCMI_ERR_ARG, "block length out of range (1..16)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_err(SMCMI_ERR_HIP, "no HIP device available: libsmcmi has no CPU fallback");
+    devmem::Owner<> tmp;
     double *dbuf = nullptr;
     const size_t nd = (size_t)3 * d + (size_t)d * d + 3;
-    HIP_TRY(hipMalloc((void **)&dbuf, nd * sizeof(double)));
+    HIP_TRY(tmp.alloc(&dbuf, nd));
     std::vector<double> hb(nd);
     memcpy(&hb[0], para_draw, sizeof(double) * d); memcpy(&hb[d], para_subset, sizeof(double) * d); memcpy(&hb[2 * d], mu, sizeof(double) * d);
     memcpy(&hb[3 * d], Sigma, sizeof(double) * d * d);
@@ -1353,7 +1316,6 @@ extern "C" int smcmi_debug_proposal_densities(const double *para_draw, const dou
     }
     double o[3] = {0.0, 0.0, 0.0};
     if (e == hipSuccess) e = hipMemcpy(o, dbuf + 3 * d + (size_t)d * d, sizeof(o), hipMemcpyDeviceToHost);
-    hipFree(dbuf);
     if (e != hipSuccess) return set_err(SMCMI_ERR_HIP, std::string("smcmi_debug_proposal_densities: ") + hipGetErrorString(e));
     if (o[2] != 0.0) return err_from_state(SMCMI_ERR_POSDEF);
     *q0 = o[0]; *q1 = o[1];
@@ -1379,5 +1341,20 @@ extern "C" int smcmi_mailbox_selftest(smcmi_handle *h, int32_t rank, int32_t wor
 extern "C" int smcmi_mailbox_active(smcmi_handle *h, int32_t *active_out) {
     if (!h || !active_out) return set_err(SMCMI_ERR_ARG, "null argument");
     *active_out = h->mbox_used ? 1 : 0;
+    return 0;
+}
+
+// (down here: the structs a handle owns - Eng2, the callback buffers - are complete types by now)
+extern "C" int smcmi_destroy(smcmi_handle *h) {
+    if (!h) return 0;
+    hipSetDevice(h->cfg.device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    if (h->nccl) smcmi_comm_release(h);
+    mbox_close_peers(h);
+    delete h->e2;
+    delete h->cbuf;
+    delete h->dcbuf;
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;                                 // (its owner gives back every buffer the handle made)
     return 0;
 }

@@ -34,7 +34,7 @@ struct Switches {
     // ---- diagnostics
     int trace = 0;                  // SMCMI_TRACE
     OptInt prof2;                   // SMCMI_PROF2=<stage>
-    int poison_alloc = 0;           // SMCMI_POISON_ALLOC: 1 poisons fresh device memory, 2 also reports each allocation
+    int poison_alloc = 0;           // SMCMI_POISON_ALLOC: 1 poisons fresh device memory, 2 also reports allocations and releases (devmem.hpp)
     std::string rccl_path;          // SMCMI_RCCL_PATH: the RCCL to dlopen first
 
     static Switches read() {

@@ -184,3 +184,32 @@ def test_switches_hpp_is_the_only_reader_of_the_environment_and_matches_the_desi
         if f.endswith((".hpp", ".hip")) and f != "switches.hpp" and re.search(r'getenv\s*\(\s*"SMCMI_', open(os.path.join(csrc, f)).read()):
             others.append(f)
     assert not others, others
+
+
+def test_devmem_hpp_is_the_only_caller_of_the_allocators():
+    """csrc/devmem.hpp owns every device and pinned allocation: the runtime's five allocator and free calls occur there and nowhere else
+    under csrc/ (a buffer allocated beside the owner is one nothing gives back on an error path)."""
+    csrc = os.path.join(ROOT, "smc.jl_amd", "csrc")
+    calls = ("hipMalloc", "hipExtMallocWithFlags", "hipHostMalloc", "hipFree", "hipHostFree")
+    pat = re.compile(r"\b(%s)\b" % "|".join(calls))
+    found = {f: set(pat.findall(open(os.path.join(csrc, f)).read())) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))}
+    assert found.pop("devmem.hpp") == set(calls)
+    others = {f: sorted(v) for f, v in found.items() if v}
+    assert not others, others
+    assert len(found) > 20, sorted(found)
+
+
+def test_the_owner_gives_everything_back_under_fault_injection(tmp_path):
+    """tests/devmem_check.hip drives csrc/devmem.hpp's Owner on a counting allocator that fails on its k-th call, for every k of three scripted
+    sequences (one shaped like smcmi_create, a regrow that fails after the release, a scoped temporary with an early return) - host code
+    under AddressSanitizer and UBSan, no device: exit status 0 and nothing on stderr."""
+    import subprocess
+
+    exe = tmp_path / "devmem_check"
+    r = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "--offload-host-only", "-O1", "-std=c++17",
+                        "-Xarch_host", "-fsanitize=address,undefined", os.path.join(ROOT, "tests", "devmem_check.hip"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stderr == "", r.stderr

@@ -155,3 +155,73 @@ def test_the_sharded_all_reduce_driver_rejects_an_unknown_resampler():
     assert again["n_stages"] == 12 and np.isfinite(again["logmdd"])
     for e in engs:
         e.close()
+
+
+# ---- who owns a handle's memory (csrc/devmem.hpp): under SMCMI_POISON_ALLOC=2 the library reports every allocation and every release with
+# one process-wide index; tests/handle_lifetime_child.py leaves that report on stderr, a "[scenario] <name>" line in front of each scenario
+def _lifetime_child(args, env_extra=None):
+    import re
+
+    env = dict(os.environ, SMCMI_POISON_ALLOC="2")
+    env.update(env_extra or {})
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "handle_lifetime_child.py"), ROOT] + args, env=env, capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    res = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    report, name = {}, None                                   # scenario -> (indices allocated, indices released, poisoned allocations)
+    for ln in p.stderr.splitlines():
+        if ln.startswith("[scenario] "):
+            name = ln[11:]
+            report[name] = ([], [], 0)
+            continue
+        made, gone = re.match(r"\[smcmi\] (?:poisoned )?allocation #(\d+) ", ln), re.match(r"\[smcmi\] released #(\d+)$", ln)
+        if made:
+            report[name][0].append(int(made.group(1)))
+            report[name] = report[name][:2] + (report[name][2] + ln.startswith("[smcmi] poisoned"),)
+        elif gone:
+            report[name][1].append(int(gone.group(1)))
+    for name, (made, gone, poisoned) in report.items():
+        print("scenario %s: %d allocations (%d of them poisoned device memory), %d releases" % (name, len(made), poisoned, len(gone)))
+    return res, report
+
+
+def _assert_all_given_back(report):
+    made = [i for m, _, _ in report.values() for i in m]
+    gone = [i for _, g, _ in report.values() for i in g]
+    assert len(set(made)) == len(made), "an allocation index was reported twice"
+    assert len(set(gone)) == len(gone), "an allocation was released twice"
+    assert set(made) == set(gone), (sorted(set(made) - set(gone)), sorted(set(gone) - set(made)))
+    for name, (m, g, _) in report.items():                    # every scenario closes its own handles
+        assert set(m) == set(g), (name, sorted(set(m) ^ set(g)))
+
+
+def test_a_failed_create_returns_everything_and_the_next_create_works():
+    """smcmi_create with n_local = 2^40, n_para = 3: the first cloud buffer cannot be allocated - an error return of the allocator, nothing is
+    launched.  SMCMI_ERR_HIP, the caller's handle pointer as it was, every reported allocation released; the next create in the same process
+    (4 096 particles) succeeds and runs."""
+    res, report = _lifetime_child(["create_failure"])
+    assert res["rc"] == -2, res                                                       # SMCMI_ERR_HIP
+    assert res["handle_untouched"], res
+    assert res["message"], res
+    _assert_all_given_back(report)
+    assert len(report["next"][0]) > 30, report["next"]                                # (the report is on: the working create shows in it)
+    assert res["next"][0] > 2 and res["next"][1], res
+
+
+def test_everything_a_handle_took_is_given_back():
+    """Create, use, destroy, four times: (a) one handle of 4 096 particles, n_para = 3 - an adaptive run on the default route (engine 2's buffers,
+    the segment tables, the note, the snapshot), a second run with n_mh_steps = n_blocks = 2 (the drawn-ahead buffer regrows), a fixed schedule
+    longer than the first (the schedule buffer regrows); (b) the same under SMCMI_ENGINE=1; (c) a group of two handles of 2 048 through
+    run_group; (d) a host-callback and a device-callback run at 2 048 particles.  After the last close() the set of allocation indices on
+    stderr equals the set of release indices.  (The library reads SMCMI_ENGINE once per process, so (b) is a child of its own.)"""
+    res, report = _lifetime_child(["lifetime", "acd"])
+    _assert_all_given_back(report)
+    assert not report["end"][0] and not report["end"][1], report["end"]
+    for s in "acd":
+        assert len(report[s][0]) > 30, (s, len(report[s][0]))
+        for n_stages, finite, _ in res[s]:
+            assert n_stages > 2 and finite, (s, res[s])
+    assert res["a"][2][0] == 320, res["a"]
+    res, report = _lifetime_child(["lifetime", "a"], {"SMCMI_ENGINE": "1"})           # (b)
+    _assert_all_given_back(report)
+    assert len(report["a"][0]) > 30 and res["a"][2][0] == 320, (res, len(report["a"][0]))
