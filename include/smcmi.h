@@ -331,6 +331,36 @@ int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, sm
 int smcmi_debug_proposal_densities(const double *para_draw, const double *para_subset, const double *mu, const double *Sigma,
                                    int32_t d, double c, double alpha, double *q0, double *q1);
 
+/* ---- posterior summaries on the device (csrc/summary.hip; src/particle.jl:495-503, 199-204, 213-218) ------------------------
+   weighted_quantiles: StatsBase's quantile(v, Weights(w), p) of parameter columns, without a sort and without a download -
+   selection on the order-preserving 64-bit key of a double, some 13 to 16 streaming passes per call (DESIGN.md "Posterior
+   summaries").  Only particles with w != 0 count.  Sort the pairs (value, weight); w1 = the first pair's weight,
+   h = p (wsum - w1) + w1; with S_k the running weight sum and k the first index with S_k > h the result is
+   v_{k-1} + (h - S_{k-1}) / (S_k - S_{k-1}) (v_k - v_{k-1}), and the largest value when there is no such k (p = 1, one particle).
+   -0.0 sorts below +0.0 (Julia's isless).  A NaN or negative (or infinite) weight, wsum == 0, p outside [0, 1], n_probs outside
+   1..SMCMI_MAX_QUANT, a column outside [0, n_para): SMCMI_ERR_ARG.  A NaN anywhere in a column: every quantile of that column is NaN.
+   Every sum follows a fixed order that depends on the handles' n_local only: two calls give the same bits.
+   best_particle: argmax of loglh (get_likeliest_particle_value) or of loglh + logprior (get_highest_posterior_particle_value);
+   the first index wins ties, a NaN ranks above everything and the first NaN wins (Julia's argmax).
+   The single-handle calls are the group of one; a lone handle that holds a shard (n_local != n_parts) gets SMCMI_ERR_UNSUPPORTED
+   from them.  The group calls take the handles of ONE process that together hold one cloud, in rank order as smcmi_run_group takes
+   them (contiguous shards; their sizes may differ): per pass the host reads every handle's partial sums and adds them in handle
+   order; the per-handle best particles are compared on the host, the lowest global id winning ties.  Ranks in several processes
+   (smcmi_run_sharded) are not served: there the per-pass sums would go through the communicator's all-gather.
+   The calls read the cloud and change nothing a later smcmi_run(continue_run = 1) depends on.  They report through their return
+   code alone: smcmi_last_error() keeps the text of the last failure of the other calls. */
+#define SMCMI_MAX_QUANT 16
+enum { SMCMI_BEST_LOGLH = 0, SMCMI_BEST_LOGPOST = 1 };
+/* out[c * n_probs + q]; columns NULL => all n_para parameter columns; columns must be < n_para */
+int smcmi_weighted_quantiles(smcmi_handle *h, const int32_t *columns, int32_t n_columns, const double *probs, int32_t n_probs,
+                             double *out);
+int smcmi_weighted_quantiles_group(smcmi_handle **hs, int32_t n, const int32_t *columns, int32_t n_columns, const double *probs,
+                                   int32_t n_probs, double *out);
+/* index_out: global 0-based particle id; value_out: the criterion's value there; para_out: n_para doubles (each may be NULL) */
+int smcmi_best_particle(smcmi_handle *h, int32_t criterion, int64_t *index_out, double *value_out, double *para_out);
+int smcmi_best_particle_group(smcmi_handle **hs, int32_t n, int32_t criterion, int64_t *index_out, double *value_out,
+                              double *para_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("SMCMI_LIBRARY") or os.path.join(os.path.dirname(_HERE
 
 MAX_PARA = 64
 MAX_CAND = 16
+MAX_QUANT = 16
+BEST = {"loglh": 0, "logpost": 1}
 
 PRIOR = {"normal": 0, "uniform": 1, "gamma": 2, "beta": 3, "invgamma": 4, "rootinvgamma": 5}
 LIK = {"none": -1, "gauss_iso": 0, "linreg": 1, "linmodel3": 2, "capm_literal": 3, "lgss_kalman": 4, "host_callback": 100}
@@ -142,6 +144,10 @@ SYMBOLS = [
     ("smcmi_mailbox_selftest", C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("smcmi_mailbox_active", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("smcmi_run_group", C.c_int, [C.POINTER(_H), C.c_int32, C.POINTER(RunConfig), C.POINTER(Result)]),
+    ("smcmi_weighted_quantiles", C.c_int, [_H, ip, C.c_int32, dp, C.c_int32, dp]),
+    ("smcmi_weighted_quantiles_group", C.c_int, [C.POINTER(_H), C.c_int32, ip, C.c_int32, dp, C.c_int32, dp]),
+    ("smcmi_best_particle", C.c_int, [_H, C.c_int32, lp, dp, dp]),
+    ("smcmi_best_particle_group", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, lp, dp, dp]),
 ]
 
 _LIB = None

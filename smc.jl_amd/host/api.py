@@ -284,6 +284,72 @@ def weighted_std(c):
     return np.sqrt(np.diag(weighted_cov(c)))
 
 
+def _weighted_quantiles_1d(v, w, probs):
+    """StatsBase's quantile(v, Weights(w), p) as it computes it: pairs with w != 0 sorted by (value, weight), a running sum S_k,
+    h = p (wsum - w1) + w1, k the first index with S_k > h, v_{k-1} + (h - S_{k-1}) / (S_k - S_{k-1}) (v_k - v_{k-1}); the largest value
+    when there is no such k.  Errors as StatsBase raises them; a NaN in v gives NaN."""
+    v, w, probs = np.asarray(v, dtype=np.float64), np.asarray(w, dtype=np.float64), np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    if not np.all((probs >= 0) & (probs <= 1)):
+        raise ValueError("input probability out of [0,1] range")
+    if np.any(np.isnan(w)) or np.any(w < 0):
+        raise ValueError("weight vector cannot contain NaN or negative entries")
+    wsum = float(w.sum())
+    if not math.isfinite(wsum):
+        raise ValueError("only finite weights are supported")
+    if wsum == 0:
+        raise ValueError("weight vector cannot sum to zero")
+    if np.any(np.isnan(v)):
+        return np.full(probs.shape, np.nan)
+    nz = w != 0
+    v, w = v[nz], w[nz]
+    order = np.lexsort((w, v))
+    v, w = v[order], w[order]
+    # (the running sum and h in extended precision where the platform has it: h - S_{k-1} cancels, and a double running sum over N weights
+    # that sum to N leaves an error of some 1e-12 of the gap v_k - v_{k-1})
+    S = np.cumsum(w.astype(np.longdouble))
+    out = np.empty(probs.shape)
+    for q, p in enumerate(probs):
+        h = np.longdouble(p) * (S[-1] - S[0]) + S[0]
+        k = int(np.searchsorted(S, h, side="right"))
+        if k >= v.size:
+            out[q] = v[-1]
+        else:
+            s_old, v_old = (S[k - 1], v[k - 1]) if k > 0 else (np.longdouble(0), 0.0)
+            out[q] = v_old + float((h - s_old) / (S[k] - s_old)) * (v[k] - v_old)
+    return out
+
+
+def weighted_quantiles(c, probs=(0.05, 0.95)):
+    """(n_params, len(probs)): the weighted quantiles of every parameter column.  On a cloud that lives on the device the same
+    numbers come from Engine.weighted_quantiles without a download."""
+    P, w = _P(c), get_weights(c)
+    return np.array([_weighted_quantiles_1d(P[:, j], w, probs) for j in range(P.shape[1] - 5)])
+
+
+def weighted_quantile(c, i):
+    """src/particle.jl:495-503: (lb, ub), the 5 % and 95 % weighted quantiles of parameter i (1-based, as in the reference)."""
+    P = _P(c)
+    assert 1 <= i <= P.shape[1] - 5, "Parameter index invalid."
+    lb, ub = _weighted_quantiles_1d(P[:, i - 1], get_weights(c), (0.05, 0.95))
+    return float(lb), float(ub)
+
+
+def _argmax(x):
+    """Julia's argmax (0-based here): the first NaN if there is one, else the first largest value"""
+    nan = np.flatnonzero(np.isnan(x))
+    return int(nan[0]) if nan.size else int(np.argmax(x))
+
+
+def get_likeliest_particle_value(c):
+    """src/particle.jl:199-204: the parameter vector of the particle with the highest log-likelihood."""
+    return np.array(_P(c)[_argmax(get_loglh(c)), :-5])
+
+
+def get_highest_posterior_particle_value(c):
+    """src/particle.jl:213-218: the parameter vector of the particle with the highest log-posterior."""
+    return np.array(_P(c)[_argmax(get_logpost(c)), :-5])
+
+
 def cloud_isempty(c):
     return len(c) == 0
 

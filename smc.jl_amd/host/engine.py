@@ -228,6 +228,16 @@ class Engine:
         check(self._L.smcmi_moments(self._h, _d(mean), _d(cov)))
         return mean, cov
 
+    def weighted_quantiles(self, columns=None, probs=(0.05, 0.95)):
+        """Weighted quantiles of parameter columns on the device (smcmi_weighted_quantiles; api.weighted_quantiles on a download gives
+        the same numbers): (len(columns), len(probs)), columns 0-based, None = every parameter."""
+        return _quantiles([self], columns, probs, single=True)
+
+    def best_particle(self, criterion="loglh"):
+        """(global 0-based index, value, parameters) of the particle with the highest log-likelihood ("loglh",
+        get_likeliest_particle_value) or log-posterior ("logpost", get_highest_posterior_particle_value)."""
+        return _best([self], criterion, single=True)
+
     def stage_moments(self):
         """(θ̄, R) the last stage used for its proposals, as the engine left them (smcmi_debug_stage_moments): nothing is recomputed."""
         mean, cov = np.empty(self.d), np.empty((self.d, self.d))
@@ -562,3 +572,52 @@ def run_group(engines, n_blocks=1, n_mh_steps=1, lam=2.1, n_phi=300, resampling_
     out = Engine._result(res)
     out["paused"] = bool(res.paused)
     return out
+
+
+_SUMMARY_ERRORS = {-1: "bad argument: a NaN / negative / infinite weight, weights that sum to zero, a probability outside [0, 1], more than "
+                       "MAX_QUANT probabilities, a column that is no parameter, or handles that are not the contiguous shards of one cloud",
+                   -2: "a HIP call failed", -7: "this handle holds a shard of its cloud: call the group function with all of its handles"}
+
+
+def _check_summary(rc):
+    """(the summaries report through their return code alone: include/smcmi.h)"""
+    if rc != 0:
+        raise _lib.SMCMIError(rc, _SUMMARY_ERRORS.get(rc, "posterior summary failed"))
+
+
+def weighted_quantiles_group(engines, columns=None, probs=(0.05, 0.95)):
+    """Weighted quantiles over the shard engines of this process that together hold one cloud (smcmi_weighted_quantiles_group), in
+    rank order as run_group takes them: (len(columns), len(probs))."""
+    return _quantiles(engines, columns, probs, single=False)
+
+
+def best_particle_group(engines, criterion="loglh"):
+    """(global 0-based index, value, parameters) of the best particle over the shard engines of one cloud (smcmi_best_particle_group);
+    the lowest global id wins ties."""
+    return _best(engines, criterion, single=False)
+
+
+def _quantiles(engines, columns, probs, single):
+    L = _lib.lib()
+    pr = _f64(np.atleast_1d(probs))
+    cols = None if columns is None else np.ascontiguousarray(np.atleast_1d(columns), dtype=np.int32)
+    out = np.empty((engines[0].d if cols is None else cols.size, pr.size))
+    cp, nc = (None, 0) if cols is None else (_i(cols), cols.size)
+    if single:
+        _check_summary(L.smcmi_weighted_quantiles(engines[0]._h, cp, nc, _d(pr), pr.size, _d(out)))
+    else:
+        arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
+        _check_summary(L.smcmi_weighted_quantiles_group(arr, len(engines), cp, nc, _d(pr), pr.size, _d(out)))
+    return out
+
+
+def _best(engines, criterion, single):
+    L = _lib.lib()
+    idx, val, para = C.c_int64(), C.c_double(), np.empty(engines[0].d)
+    crit = _lib.BEST[criterion]
+    if single:
+        _check_summary(L.smcmi_best_particle(engines[0]._h, crit, C.byref(idx), C.byref(val), _d(para)))
+    else:
+        arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
+        _check_summary(L.smcmi_best_particle_group(arr, len(engines), crit, C.byref(idx), C.byref(val), _d(para)))
+    return idx.value, val.value, para

@@ -3,7 +3,7 @@
 # Keeps the reference's entry point and types for the correction / selection / mutation loop:
 #
 #     smc(loglikelihood::Function, parameters::ParameterVector, data::Matrix; kwargs...)      src/smc_main.jl:118-161
-#     Cloud, get_vals / get_loglh / ... / weighted_mean / weighted_cov                          src/particle.jl
+#     Cloud, get_vals / get_loglh / ... / weighted_mean / weighted_cov / weighted_quantile      src/particle.jl
 #
 # and hands the loop (src/smc_main.jl:377-508) to the MI355X engine.  The user's closure is bound through
 # `smcmi_set_likelihood_callback`: one `@cfunction` trampoline evaluates the closure on the batch of proposals that passed the
@@ -22,7 +22,9 @@ using ModelConstructors, Distributions, Random, Dates
 import JLD2, HDF5, LinearAlgebra
 
 export smc, Cloud, get_vals, get_loglh, get_logprior, get_old_loglh, get_logpost, get_accept, get_weights, weighted_mean, weighted_cov,
-       weighted_std, cloud_isempty, GaussIso, LinReg, LinModel3, CapmLiteral, LGSSKalman,
+       weighted_std, weighted_quantile, weighted_quantiles, get_likeliest_particle_value, get_highest_posterior_particle_value,
+       device_weighted_quantiles, device_weighted_quantiles_group, device_best_particle, device_best_particle_group,
+       cloud_isempty, GaussIso, LinReg, LinModel3, CapmLiteral, LGSSKalman,
        mutation, resample, mvnormal_mixture_draw, initial_draw!, get_cloud                       # src/SMC.jl:13-17
 
 const LIB = get(ENV, "SMCMI_LIB", joinpath(@__DIR__, "..", "csrc", "libsmcmi.so"))
@@ -97,6 +99,41 @@ function weighted_cov(c::Cloud)                      # StatsBase.cov(X, Weights(
 end
 weighted_std(c::Cloud) = sqrt.(diag_of(weighted_cov(c)))
 diag_of(A) = [A[i, i] for i in 1:size(A, 1)]
+# StatsBase's quantile(v, Weights(w), p) for non-frequency weights (src/particle.jl:495-503 calls it at 0.05 and 0.95; DESIGN.md "Posterior
+# summaries" states the definition): pairs with w != 0 sorted by (value, weight), h = p (wsum - w1) + w1, k the first index with S_k > h
+function weighted_quantiles(v::AbstractVector{Float64}, w::AbstractVector{Float64}, probs)
+    all(p -> 0 <= p <= 1, probs) || throw(ArgumentError("input probability out of [0,1] range"))
+    any(x -> isnan(x) || x < 0, w) && throw(ArgumentError("weight vector cannot contain NaN or negative entries"))
+    wsum = sum(w)
+    isfinite(wsum) || throw(ArgumentError("only finite weights are supported"))
+    wsum == 0 && throw(ArgumentError("weight vector cannot sum to zero"))
+    any(isnan, v) && return fill(NaN, length(probs))
+    nz = w .!= 0
+    vw = sort!(collect(zip(v[nz], w[nz])))
+    w1 = vw[1][2]
+    out = fill(vw[end][1], length(probs))
+    for (q, p) in enumerate(probs)
+        h = p * (wsum - w1) + w1
+        Sk = 0.0; Skold = 0.0; vk = 0.0; vkold = 0.0
+        for (x, wk) in vw
+            Skold, vkold = Sk, vk
+            vk = x; Sk += wk
+            if Sk > h
+                out[q] = vkold + (h - Skold) / (Sk - Skold) * (vk - vkold)
+                break
+            end
+        end
+    end
+    out
+end
+weighted_quantiles(c::Cloud, probs = (0.05, 0.95)) = [weighted_quantiles(c.particles[:, i], get_weights(c), probs) for i in 1:n_para(c)]
+function weighted_quantile(c::Cloud, i::Integer)                                                 # src/particle.jl:495-503
+    @assert i <= n_para(c) "Parameter index invalid."
+    lb, ub = weighted_quantiles(c.particles[:, i], get_weights(c), (0.05, 0.95))
+    return lb, ub
+end
+get_likeliest_particle_value(c::Cloud) = c.particles[argmax(get_loglh(c)), 1:n_para(c)]          # src/particle.jl:199-204
+get_highest_posterior_particle_value(c::Cloud) = c.particles[argmax(get_logpost(c)), 1:n_para(c)]   # src/particle.jl:213-218
 
 # ---- device likelihood families standing in for the closure (SMCMI_LIK_* in smcmi.h)
 struct GaussIso; sigma::Float64; end
@@ -322,6 +359,39 @@ function stage_records(h::Handle)
     check(ccall((:smcmi_get_stage_records, LIB), Cint, (Handle, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
                 h, phi, ess, cs, acc, rs))
     return phi, ess, cs, acc, rs
+end
+# ---- posterior summaries of a cloud that lives on the device (smcmi.h "posterior summaries"): no download, no sort.  They report through
+# their return code alone (-1 bad argument, -2 HIP, -7 a lone shard).  columns: 1-based parameter indices, `nothing` = all d of them.
+check_summary(rc) = rc == 0 ? nothing : error("smcmi posterior summary failed with code $rc")
+summary_columns(columns, d) = columns === nothing ? (Ptr{Int32}(C_NULL), Int32(0), Int(d)) : (Int32[c - 1 for c in columns], Int32(length(columns)), length(columns))
+function device_weighted_quantiles(h::Handle, d::Integer; columns = nothing, probs = (0.05, 0.95))
+    cols, nc, rows = summary_columns(columns, d)
+    pr = Float64[p for p in probs]
+    out = Matrix{Float64}(undef, length(pr), rows)                                               # out[c * n_probs + q]: column-major (q, c)
+    check_summary(ccall((:smcmi_weighted_quantiles, LIB), Cint, (Handle, Ptr{Int32}, Int32, Ptr{Float64}, Int32, Ptr{Float64}),
+                        h, cols, nc, pr, Int32(length(pr)), out))
+    return permutedims(out)
+end
+function device_weighted_quantiles_group(hs::Vector{Handle}, d::Integer; columns = nothing, probs = (0.05, 0.95))
+    cols, nc, rows = summary_columns(columns, d)
+    pr = Float64[p for p in probs]
+    out = Matrix{Float64}(undef, length(pr), rows)
+    check_summary(ccall((:smcmi_weighted_quantiles_group, LIB), Cint, (Ptr{Handle}, Int32, Ptr{Int32}, Int32, Ptr{Float64}, Int32, Ptr{Float64}),
+                        hs, Int32(length(hs)), cols, nc, pr, Int32(length(pr)), out))
+    return permutedims(out)
+end
+# (1-based global particle index, value, parameters); criterion :loglh (get_likeliest_particle_value) or :logpost (get_highest_posterior_particle_value)
+const BEST = Dict(:loglh => Int32(0), :logpost => Int32(1))
+function device_best_particle(h::Handle, d::Integer; criterion::Symbol = :loglh)
+    idx = Ref{Int64}(0); val = Ref{Float64}(0.0); para = Vector{Float64}(undef, d)
+    check_summary(ccall((:smcmi_best_particle, LIB), Cint, (Handle, Int32, Ref{Int64}, Ref{Float64}, Ptr{Float64}), h, BEST[criterion], idx, val, para))
+    return Int(idx[]) + 1, val[], para
+end
+function device_best_particle_group(hs::Vector{Handle}, d::Integer; criterion::Symbol = :loglh)
+    idx = Ref{Int64}(0); val = Ref{Float64}(0.0); para = Vector{Float64}(undef, d)
+    check_summary(ccall((:smcmi_best_particle_group, LIB), Cint, (Ptr{Handle}, Int32, Int32, Ref{Int64}, Ref{Float64}, Ptr{Float64}),
+                        hs, Int32(length(hs)), BEST[criterion], idx, val, para))
+    return Int(idx[]) + 1, val[], para
 end
 # parity aid: (θ̄, R) the last stage used for its proposals, as the engine left them (row-major on the C side; R before (R + R') / 2)
 function stage_moments(h::Handle, d::Integer)
