@@ -279,16 +279,20 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     h->cb_calls = 0; h->cb_evals = 0;
     double *phase_ms = cb_phase_ms(h);
     for (int k = 0; k < CBP_N; ++k) phase_ms[k] = 0.0;
+    const StageRun run{adaptive, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb};
     res->solver_stalls = 0; res->select_stalls = 0; res->spec_stalls = 0;
-    int launched = 0, done = 0, had = first_passes;
+    int launched = 0, done = 0;
     DevState head;
     constexpr size_t head_off = offsetof(DevState, stage), head_len = offsetof(DevState, ess) - offsetof(DevState, stage);
     while (launched < max_iter && !done) {
         // the stage up to the proposal set-up (no mutation kernel: host_mutation below); no energy sums exist for a predictor
         const double ts0 = cb_now_ms();
-        const int passes = (h->cb_energy && launched >= 2) ? std::max(1, rc->solver_passes) : first_passes;
-        enqueue_stage(h, adaptive, passes, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb, nullptr, nullptr, 0, false, false, false, false, true);
-        had = passes;
+        StageReq q; q.host_mut = true;
+        q.passes = (h->cb_energy && launched >= 2) ? std::max(1, rc->solver_passes) : first_passes;
+        enqueue_stage(h, run, q);
+        // One book per stage, as the ladder of its passes only (q.passes, then 8 more per stall, up to the bracket guard): the stage is synced before the
+        // next goes out and earlier stalls do not raise its passes - both counts are q.passes, and the stage number only has to stay the same.
+        stagepolicy::StallBook book(q.passes, q.passes, 8, base, false);
         bool first_enqueued = false;
         for (;;) {
             HIP_TRY(hipMemcpyAsync((char *)&head + head_off, (const char *)h->d_st + head_off, head_len, hipMemcpyDeviceToHost, h->stream));
@@ -309,12 +313,12 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
             first_enqueued = false;
             HIP_TRY(hipStreamSynchronize(h->cbuf->s_down));          // (the dropped proposal's copies: the pinned buffers are reused below)
             }
-            if (had > 1200) return set_err(SMCMI_ERR_BRACKET, "adaptive tempering solver: the search for phi_n does not terminate (the ESS objective is not a number?)");
-            // the solver ran out of passes: continue the same search with more (smcmi_run)
+            const auto more = book.solver_stall(base + launched + 2);
+            if (!more.ok) return bracket_error();
             const int zero = 0;
             HIP_TRY(hipMemcpyAsync(&h->d_st->done, &zero, sizeof(int), hipMemcpyHostToDevice, h->stream));
-            enqueue_stage(h, adaptive, 8, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb, nullptr, nullptr, had, false, false, false, false, true);
-            had += 8;
+            q.p0 = more.p0; q.passes = more.p1 - more.p0;
+            enqueue_stage(h, run, q);
             res->solver_stalls += 1;
         }
         phase_ms[CBP_STAGE] += cb_now_ms() - ts0;

@@ -5,27 +5,50 @@
 
 // ------------------------------------------------------------------------------------------------ whole loop
 // One stage = a fixed kernel sequence (no host decision inside): see the header of kernels.hpp.
-// p0 > 0 resumes a stage whose solver ran out of passes after p0 of them (st->done == 2 stall, see solver_prologue): the
-// search continues with passes p0 .. p0 + solver_passes - 1 exactly as if the original list had been that much longer.
-// no_select: the host expects no resampling in this stage: k_post_correct and k_resample_gather are not launched, the moments
-// kernel takes the decision itself and stalls the run (done = 3) if selection is needed after all.
-// tail_only: resume such a stage from k_post_correct on (the correction is already done).
-static void enqueue_stage(smcmi_handle *h, bool adaptive, int solver_passes, int method, int n_blocks, double alpha, int acc_nb,
-                          hipEvent_t ev0, hipEvent_t ev1, int p0 = 0, bool no_select = false, bool tail_only = false, bool spec = false,
-                          bool skip_begin = false, bool host_mut = false) {
+struct StageRun { bool adaptive; int method, n_blocks; double alpha; int acc_nb; };      // what all stages of a run share
+// what varies from one enqueue to the next; every caller sets only what it means
+struct StageReq {
+    int passes = 0;             // solver passes to enqueue
+    // p0 > 0 resumes a stage whose solver ran out of passes after p0 of them (st->done == 2 stall, see solver_prologue): the
+    // search continues with passes p0 .. p0 + passes - 1 exactly as if the original list had been that much longer.
+    int p0 = 0;
+    // the host expects no resampling in this stage: k_post_correct and k_resample_gather are not launched, the moments
+    // kernel takes the decision itself and stalls the run (done = 3) if selection is needed after all.
+    bool no_select = false;
+    bool tail_only = false;     // resume such a stage from k_post_correct on (the correction is already done)
+    bool spec = false;          // predict -> correct -> verify (kernels.hpp k_stage_begin): no certificate pass is enqueued at all - 4 launches
+    bool skip_begin = false;    // resume of such a stage through the certificate path: its begin has run
+    bool host_mut = false;      // the mutation runs through the host callback (callback.hpp): none is launched
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;     // profile mode: recorded around the mutation launch
+};
+// What resumes stage st, stalled with DevState::done = 2 (its solver ran out of passes: the same search continues with more), 3 (enqueued
+// without selection kernels it must resample after all: nothing past its correction has run - the rest of it through the full path) or 4
+// (enqueued without a certificate pass, its prediction did not verify: nothing is committed, W̃ went to scratch - the caller re-arms the solver
+// and the stage runs through the certificate path); booked in `book`.  false: the search of a done = 2 stage does not terminate.
+static bool resume_request(stagepolicy::StallBook &book, int done, int st, StageReq *q) {
+    if (done == 4) { q->passes = book.first_passes; q->skip_begin = true; book.spec_stall(st); }
+    else if (done == 2) {
+        const auto more = book.solver_stall(st);
+        if (!more.ok) return false;
+        q->p0 = more.p0; q->passes = more.p1 - more.p0;
+    } else { q->p0 = book.had(st); q->tail_only = true; book.select_stall(); }
+    return true;
+}
+static void enqueue_stage(smcmi_handle *h, const StageRun &run, const StageReq &q) {
+    const bool adaptive = run.adaptive, no_select = q.no_select, tail_only = q.tail_only, host_mut = q.host_mut;
+    const int p0 = q.p0, acc_nb = run.acc_nb;
     const long long n = h->n;
     hipStream_t s = h->stream;
-    // spec: predict -> correct -> verify (kernels.hpp k_stage_begin): no certificate pass is enqueued at all - 4 launches
-    const int P = (adaptive && !spec) ? p0 + solver_passes : 0;
+    const int P = (adaptive && !q.spec) ? p0 + q.passes : 0;
     h->run_adaptive = adaptive;
     const int fin_slot = P == 0 ? 0 : (P & 1);
     // no selection expected and the register kernels apply: the correction pass gathers the moments too, k_prepare_mutation
     // takes the post-correction decision, the mutation kernel normalises the weights (5 launches per stage)
     const bool cm = no_select && !tail_only && can_fuse_cm(h);
     h->fused_cm = cm;
-    h->spec_stage = spec && cm;
+    h->spec_stage = q.spec && cm;
     if (!tail_only) {
-    if (p0 == 0 && !skip_begin) {
+    if (p0 == 0 && !q.skip_begin) {
         // (a host-callback mutation without cb_energy - sharded closure runs, fixed schedules - leaves neither energy sums nor energy maxima:
         // plain schedule walk, unshifted weights)
         const bool hm_plain = host_mut && !h->cb_energy;
@@ -51,23 +74,23 @@ static void enqueue_stage(smcmi_handle *h, bool adaptive, int solver_passes, int
     int nbm = 0;
     if (cm) {
         launch_prepare_in_run(h, h->d_part_cm, h->nb_e, 3, fin_slot);
-        if (ev0) hipEventRecord(ev0, s);
-        launch_mutate(h, n_blocks, 0, alpha);
-        if (ev1) hipEventRecord(ev1, s);
+        if (q.ev0) hipEventRecord(q.ev0, s);
+        launch_mutate(h, run.n_blocks, 0, run.alpha);
+        if (q.ev1) hipEventRecord(q.ev1, s);
         return;
     }
     if (no_select && !tail_only && can_fuse_post(h)) nbm = launch_moments(h, h->d_hist_W, 0, fin_slot);
     else {
         k_post_correct<<<h->nb_e, TB, 0, s>>>(h->d_st, h->d_part_fin, h->nb_e, nullptr, h->rec, fin_slot, h->cl, h->d_cum);
-        k_resample_gather<<<(unsigned)std::min<long long>((n + TB - 1) / TB, 4 * h->noop_grid), TB, 0, s>>>(h->cl, h->d_st, h->d_cum, n, 0, h->cfg.n_parts, method,
+        k_resample_gather<<<(unsigned)std::min<long long>((n + TB - 1) / TB, 4 * h->noop_grid), TB, 0, s>>>(h->cl, h->d_st, h->d_cum, n, 0, h->cfg.n_parts, run.method,
                                                                      h->cfg.seed, 0u, nullptr, h->d_anc, nullptr, 0);
         nbm = launch_moments(h, h->d_hist_W, 0);
     }
     launch_prepare_in_run(h, h->d_part_mom, nbm, 1);
-    if (host_mut) return;                   // the mutation runs through the host callback (callback.hpp)
-    if (ev0) hipEventRecord(ev0, s);
-    launch_mutate(h, n_blocks, 0, alpha);
-    if (ev1) hipEventRecord(ev1, s);
+    if (host_mut) return;
+    if (q.ev0) hipEventRecord(q.ev0, s);
+    launch_mutate(h, run.n_blocks, 0, run.alpha);
+    if (q.ev1) hipEventRecord(q.ev1, s);
 }
 
 // a (host closure, device family) pair in a tempered update: the callback path would score the old likelihood as 0, the device path
@@ -101,19 +124,15 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
     if (!cont) { if (int e = first_records(h, rc)) return e; }
     if (sw().prof2.set && !h->d_prof) { if (dmalloc(h->mem, &h->d_prof, 32)) return SMCMI_ERR_HIP; }
     if (int e = ensure_zbuf(h, rc->n_mh_steps, rc->n_blocks)) return e;
-    const int solver_passes = rc->solver_passes >= 1 ? rc->solver_passes : DEFAULT_SOLVER_PASSES;
-    const int first_passes = std::max(solver_passes, FIRST_SOLVER_PASSES);
+    const int first_passes = std::max(rc->solver_passes >= 1 ? rc->solver_passes : DEFAULT_SOLVER_PASSES, FIRST_SOLVER_PASSES);
     const int sync_every = rc->sync_every > 0 ? rc->sync_every : 32;     // (16 until round 4: 36.75 vs 36.45 ms per run at N = 1e6)
     const int acc_nb = mut_blocks(h);
     // largest energy of the initial cloud, in the layout the mutation epilogue uses afterwards (stage 1's energy shift)
     k_energy_max<<<acc_nb, TB, 0, h->stream>>>(h->cl, h->d_st, h->d_emax_part);
-    const bool profile = rc->use_graph == 2;    // 2 = direct launches with HIP events around the mutation kernel
-    std::vector<hipEvent_t> evs;
-    std::vector<int> ev_iter;      // profile mode: iteration each event pair belongs to, -1 once known to have bracketed a no-op
-    // Resampling is predictable on an adaptive schedule (every stage ends at ESS = target x the previous ESS, or x N after a
-    // resample), so the host enqueues the selection kernels only where it expects a resample; the device checks the expectation
-    // (k_moments_reg) and stalls the run if it was wrong.  SMCMI_NO_SELECT_PREDICT=1 (development) keeps the full list everywhere,
-    // =2 deliberately predicts "never" to exercise the stall path.
+    const StageRun run{adaptive, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb};
+    MutationEvents evs(rc->use_graph == 2);     // tagged with the iteration of the launch
+    // The selection kernels go only where a resample is forecast (stagepolicy.hpp Forecast; k_moments_reg checks the expectation).
+    // SMCMI_NO_SELECT_PREDICT=1 (development) keeps the full list everywhere, =2 deliberately predicts "never" to exercise the stall path.
     const int sel_mode = sw().no_select_predict;
     // (Fixed schedules: extrapolating the ESS decay was tried and dropped - CAPM-like posteriors collapse within two or three
     // stages, 19 of 20 resamples stalled, and the per-batch sync it needs makes short stages host-bound.)
@@ -143,24 +162,15 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
     // produces cannot verify a predicted root: those runs keep the certificate pass)
     const bool spec_ok = predict_select && can_fuse_cm(h) && !sw().no_predictor &&
                          rc->tempered_update_prior_weight == 0.0 && rp.phi_rtol > 0.0;
-    double pred_ess = cont ? s.ess_prev : initial_ess(h, rc);   // ESS after the last completed stage
-    int pred_rl = cont ? s.resampled_last : 0;                                             // resampled_last_period
+    stagepolicy::Forecast forecast(rc->tempering_target, (double)h->cfg.n_parts, rp.threshold, cont ? s.ess_prev : initial_ess(h, rc), cont ? s.resampled_last : 0);
+    stagepolicy::StallBook book(first_passes, stagepolicy::starting_passes(rc->solver_passes, DEFAULT_SOLVER_PASSES, rc->tempering_target), 8, base, spec_ok);
+    stagepolicy::StagesLeft left;
     const auto t0 = std::chrono::steady_clock::now();
     int launched = 0, done = 0;
-    res->solver_stalls = 0; res->select_stalls = 0; res->spec_stalls = 0;
+    const StallReport stall_report{res, book};
     const int max_iter = (adaptive ? h->cfg.max_stages : rc->n_phi - 1) - base;
-    int stall_stage = -1, stall_p = 0;        // stage that last ran out of solver passes and how many it has had so far
-    int dyn_P = solver_passes;                // passes enqueued per stage: raised when stalls are frequent (poorly predictable models)
-    // Predict-correct-verify pays only while predictions verify: three failures, each within four stages of the one before
-    // (heavy-tailed energies, steps too long for the 16-term model), switch the rest of the run to the certificate path,
-    // where a miss costs an extra pass instead of a host round trip.
-    bool spec_on = spec_ok;
-    int last_spec_stall = -100, spec_strikes = 0, last_solver_stall = -100;
-    if (rc->solver_passes < 1 && rc->tempering_target < 0.95) dyn_P = 2;   // larger steps: the 8-term model is good to ~1e-3 only, two passes are the norm
-    int stages_left_est = 1 << 30;             // from the last sync: (1 - ϕ_n) / (ϕ_n - ϕ_{n-1}), an over-estimate while the steps grow
     while (launched < max_iter && !done) {
-        // near the end of the run the batch shrinks to what is left, so that few no-op stages trail the one that reaches ϕ = 1
-        int batch = adaptive ? std::min(std::min(sync_every, std::max(stages_left_est, 4)), max_iter - launched) : max_iter - launched;
+        int batch = adaptive ? left.batch(sync_every, max_iter - launched) : max_iter - launched;
         for (int b = 0; b < batch; ++b) {
             bool no_select = false;
             if (fixed_ns) {
@@ -178,12 +188,11 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
                     const int st_i = h->h_note[0];
                     h->h_note[1] = 0;
                     HIP_TRY(hipMemsetAsync(&h->d_st->done, 0, sizeof(int), h->stream));
-                    for (int &it : ev_iter)
-                        if (it >= st_i - 2 - base) it = -1;           // the stalled stage and everything behind it were no-ops
-                    hipEvent_t r0 = nullptr, r1 = nullptr;
-                    if (profile) { hipEventCreate(&r0); hipEventCreate(&r1); evs.push_back(r0); evs.push_back(r1); ev_iter.push_back(st_i - 2 - base); }
-                    enqueue_stage(h, adaptive, 0, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb, r0, r1, 0, false, true);
-                    res->select_stalls += 1;
+                    StageReq q; q.tail_only = true;
+                    evs.void_from(st_i - 2 - base);
+                    evs.pair(st_i - 2 - base, &q.ev0, &q.ev1);
+                    enqueue_stage(h, run, q);
+                    book.select_stall();
                     launched = st_i - 1 - base;
                     batch = max_iter - launched; b = -1;
                     continue;
@@ -191,20 +200,13 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
                 if (leave) break;
                 no_select = true;
             }
-            if (predict_select) {
-                // ESS this stage will end at (helpers.jl:14-20), with a margin: a wrong "resample" guess only costs two idle launches
-                const double ess_bar = rc->tempering_target * (pred_rl ? (double)h->cfg.n_parts : pred_ess);
-                const bool rs = ess_bar < rp.threshold * (1.0 + 1e-6);
-                no_select = !rs || sel_mode == 2;
-                pred_ess = ess_bar; pred_rl = rs ? 1 : 0;
-            }
-            const bool spec = spec_on && no_select && launched >= 2;
-            {
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (profile) { hipEventCreate(&e0); hipEventCreate(&e1); evs.push_back(e0); evs.push_back(e1); ev_iter.push_back(launched); }
-                enqueue_stage(h, adaptive, launched < 2 ? first_passes : dyn_P, rc->resampling_method, rc->n_blocks, rc->alpha,
-                              acc_nb, e0, e1, 0, no_select, false, spec);
-            }
+            if (predict_select) no_select = !forecast.step() || sel_mode == 2;
+            StageReq q;
+            q.passes = book.fresh(launched);
+            q.no_select = no_select;
+            q.spec = book.spec_on && no_select && launched >= 2;
+            evs.pair(launched, &q.ev0, &q.ev1);
+            enqueue_stage(h, run, q);
             ++launched;
         }
         // one copy per sync: the loop scalars from `stage` to `ess_prev` are contiguous in DevState (64 bytes) - the done flag, the
@@ -220,42 +222,14 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
             if (pull_state(h)) return SMCMI_ERR_HIP;
             if (fixed_ns) h->h_note[1] = 0;               // (the stream is drained: no post is in flight)
             const int st_i = s.stage;
-            const int had = (st_i == stall_stage) ? stall_p : (st_i - base <= 3 ? first_passes : dyn_P);
             const int zero = 0;
             HIP_TRY(hipMemcpyAsync(&h->d_st->done, &zero, sizeof(int), hipMemcpyHostToDevice, h->stream));
-            for (int &it : ev_iter)
-                if (it >= st_i - 2 - base) it = -1;           // the stalled stage and everything behind it were no-ops
-            hipEvent_t r0 = nullptr, r1 = nullptr;
-            if (profile) { hipEventCreate(&r0); hipEventCreate(&r1); evs.push_back(r0); evs.push_back(r1); ev_iter.push_back(st_i - 2 - base); }
-            if (done == 4) {
-                // A stage enqueued without a certificate pass had no usable prediction, or the ESS its correction produced did
-                // not verify it: nothing of the stage has been committed (W̃ went to scratch).  Re-arm the solver with the plain
-                // schedule walk and run the stage through the certificate-pass path.
-                k_solver_rearm<<<1, 64, 0, h->stream>>>(h->d_st, h->d_sched);
-                enqueue_stage(h, adaptive, first_passes, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb, r0, r1, 0, false, false, false, true);
-                stall_stage = st_i; stall_p = first_passes;
-                res->spec_stalls += 1;
-                if (st_i - last_spec_stall <= 4) { if (++spec_strikes >= 2) spec_on = false; }
-                else spec_strikes = 0;
-                last_spec_stall = st_i;
-            } else if (done == 2) {
-                // A stage exhausted its solver passes: it and everything enqueued behind it did nothing.  Clear the stall, give
-                // that stage more passes (continuing the same search), and go on from the stage after it.
-                const int more = 8;
-                if (had > 1200) return set_err(SMCMI_ERR_BRACKET, "adaptive tempering solver: the search for phi_n does not terminate (the ESS objective is not a number?)");
-                enqueue_stage(h, adaptive, more, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb, r0, r1, had);
-                stall_stage = st_i; stall_p = had + more;
-                res->solver_stalls += 1;
-                // a stall flushes the rest of its batch and costs a host round trip, an idle pass launch costs 3 µs: two stalls
-                // within four stages -> enqueue one more pass per stage from here on
-                if (st_i - last_solver_stall <= 4 && dyn_P < 4) ++dyn_P;
-                last_solver_stall = st_i;
-            } else {
-                // A stage enqueued without selection kernels needs to resample after all: nothing past its correction has run.
-                // Run the rest of that stage with the full path, then go on from the stage after it.
-                enqueue_stage(h, adaptive, 0, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb, r0, r1, had, false, true);
-                res->select_stalls += 1;                   // selection stalls (diagnostic)
-            }
+            StageReq q;
+            evs.void_from(st_i - 2 - base);
+            evs.pair(st_i - 2 - base, &q.ev0, &q.ev1);
+            if (done == 4) k_solver_rearm<<<1, 64, 0, h->stream>>>(h->d_st, h->d_sched);       // (with the plain schedule walk)
+            if (!resume_request(book, done, st_i, &q)) return bracket_error();
+            enqueue_stage(h, run, q);                      // ... and go on from the stage after it
             launched = st_i - 1 - base;
             HIP_TRY(hipMemcpyAsync(&done, &h->d_st->done, sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
@@ -268,16 +242,11 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
         // batch (config 2: 256 stages = 16 batches of 16) nothing has raised it yet - do not enqueue a whole batch of no-ops (64
         // launches and a sync) to find out: the closing k_stage_begin below does the same bookkeeping.
         if (!done && head.phi_n >= 1.0) break;
-        if (head.phi_n > head.phi_prev && head.phi_n < 1.0) {
-            const double left = (1.0 - head.phi_n) / (head.phi_n - head.phi_prev);
-            stages_left_est = left < 1e6 ? (int)left + 1 : 1 << 30;
-        }
+        left.observe(head.phi_n, head.phi_n - head.phi_prev);
         if (predict_select) {
-            // re-anchor the expectation on the device's ESS / flag after every sync
             s.resampled_last = head.do_resample;       // did the last stage resample
             s.ess_prev = head.ess_prev;
-            pred_ess = s.ess_prev;
-            pred_rl = s.resampled_last;
+            forecast.anchor(s.ess_prev, s.resampled_last);
         }
         if (sw().trace) {   // development only
             static long long last_passes = 0;
@@ -306,13 +275,7 @@ static int run1_impl(smcmi_handle *h, const smcmi_run_config *rc, smcmi_result *
     k_stage_begin<<<1, BT, 0, h->stream>>>(h->d_st, h->d_sched, h->d_acc_part, acc_nb, h->rec);
     if (pull_state(h)) return SMCMI_ERR_HIP;
     const auto t1 = std::chrono::steady_clock::now();
-    res->kernel_ms_mutate = 0.0; res->n_mutate_launches = 0;
-    const double ev_overhead_ms = (profile && !evs.empty()) ? event_overhead_ms(h) : 0.0;
-    for (size_t k = 0; k + 1 < evs.size(); k += 2) {
-        float ms = 0.f;
-        if (ev_iter[k / 2] >= 0 && ev_iter[k / 2] < s.stage - 1 - base && hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) { res->kernel_ms_mutate += std::max(0.0, (double)ms - ev_overhead_ms); res->n_mutate_launches += 1; }
-    }
-    for (hipEvent_t e : evs) hipEventDestroy(e);
+    if (int e = evs.tally(h, s.stage - 1 - base, res)) return e;
     finish_result(res, s, t0, t1);
     h->last_n_stages = s.stage;
     if (s.err == SMCMI_ERR_NAN_ESS) return nan_ess_error(h, h->spec_stage ? h->d_wt : h->cl.buf[0] + (long long)(h->R - 1) * h->n);

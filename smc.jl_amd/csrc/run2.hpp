@@ -309,7 +309,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         HIP_TRY(hipStreamSynchronize(h0->stream));
         e3 = bad == 0.0;
     }
-    std::vector<hipEvent_t> evs3;
+    devmem::Handles evs3;        // profile mode: a pair around every segment launch whose stage count is kept (destroyed on every return)
     int seg_launches = 0;
     // a stage that must resample does so inside the segment (stage3.hpp SELECTION): one handle, its own tables
     // (development, SMCMI_SEG_SELECT=0: the segment leaves, selection as launches)
@@ -377,8 +377,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         }
     }
     const bool profile = rc->use_graph == 2;
-    std::vector<hipEvent_t> evs;
-    std::vector<int> ev_stage;
+    MutationEvents evs(profile);                 // tagged with the stage of the launch
     const int dbg = 0;           // (the mutation kernels' ablation bits: retired as a switch in round 6)
     // large shards with helper blocks: the stage whose decision + proposal K1's helper leaves in Prop2Glob (no k2_prepare launch for it), and
     // the stage whose begin the mutation launch in front of it ran (no k2_begin launch for it) with that spec_expected
@@ -486,6 +485,17 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             }
         return publish(&Eng2::rows_gm, &Eng2::vt_gm, g0.nbg, np, -1);
     };
+    // what the mutation launch and the segment launch of stage n hand their kernels alike
+    auto mut_args = [&](smcmi_handle *h, int n, int sel_enqueued, const Rows2 &cr) {
+        Mut2Args ma{};
+        ma.seed = h->cfg.seed; ma.gid0 = h->cfg.gid0; ma.n = n; ma.sel_enqueued = sel_enqueued; ma.adaptive = adaptive ? 1 : 0;
+        ma.cmrows = cr; ma.gmrows = gm_rows(h); ma.wt = h->d_wt; ma.rows_mut = h->e2->rows_mut;
+        ma.lik[0] = h->h_model.lik[0]; ma.lik[1] = h->h_model.lik[1];
+        ma.n_steps = rc->n_mh_steps; ma.store_history = h->cfg.store_history; ma.has_other = h->h_model.has_other_priors;
+        ma.alpha = rc->alpha; ma.n_parts = (double)h->cfg.n_parts;
+        ma.hist_W = h->d_hist_W; ma.hist_ld = h->n; ma.rec = h->rec; ma.debug = dbg;
+        return ma;
+    };
     // next_begin: -1 none; 0 / 1: the launch's helper block runs stage n + 1's begin with that spec_expected (large shards with the mailbox)
     auto enq_K2 = [&](int n, int sel_enqueued, int next_begin = -1) -> int {
         last_note_seq = -1;
@@ -496,16 +506,10 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             smcmi_handle *h = g.hs[hk];
             HIP_TRY(hipSetDevice(h->cfg.device));
             Eng2 *e = h->e2;
-            Mut2Args ma{};
-            ma.seed = h->cfg.seed; ma.gid0 = h->cfg.gid0; ma.n = n; ma.sel_enqueued = sel_enqueued; ma.adaptive = adaptive ? 1 : 0;
-            ma.cmrows = crs[hk]; ma.gmrows = gm_rows(h); ma.wt = h->d_wt; ma.rows_mut = e->rows_mut;
+            Mut2Args ma = mut_args(h, n, sel_enqueued, crs[hk]);
             ma.zbuf = e->rng_ahead ? h->d_zbuf : nullptr;
             ma.tail = mb_tail(h, 1, e->vt_mut + (size_t)e->g.v0 * RMUT);
             ma.pre = inker ? nullptr : e->d_pre;
-            ma.lik[0] = h->h_model.lik[0]; ma.lik[1] = h->h_model.lik[1];
-            ma.n_steps = rc->n_mh_steps; ma.store_history = h->cfg.store_history; ma.has_other = h->h_model.has_other_priors;
-            ma.alpha = rc->alpha; ma.n_parts = (double)h->cfg.n_parts;
-            ma.hist_W = h->d_hist_W; ma.hist_ld = h->n; ma.rec = h->rec; ma.debug = dbg;
             ma.prof = (e->d_prof && n == e->prof_stage) ? e->d_prof + PROF2_K2 : nullptr;
             if (!inker && prepared_stage != n) {                // decision + proposal once, by one block (unless K1's helper block left them)
                 Mut2Args mp = ma;
@@ -515,7 +519,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
 #undef SMCMI_CALL
             }
             hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (profile && h == h0) { hipEventCreate(&e0); hipEventCreate(&e1); evs.push_back(e0); evs.push_back(e1); ev_stage.push_back(n); hipEventRecord(e0, h->stream); }
+            if (h == h0) { evs.pair(n, &e0, &e1); if (e0) hipEventRecord(e0, h->stream); }
             if (!inker && !g0.wide) {
                 // 256-particle blocks (stage2b.hpp); the drawn-ahead numbers only where this stage's K1 carried the drawing blocks
                 Beg2Args bb{};
@@ -555,14 +559,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             e->seg_seq = 1;
             if (e->h_note3) { HIP_TRY(hipStreamSynchronize(h->stream)); *(volatile int *)e->h_note3 = -1; }      // (once in 65 535 launches)
         }
-        Mut2Args ma{};
-        ma.seed = h->cfg.seed; ma.gid0 = h->cfg.gid0; ma.n = n_first; ma.sel_enqueued = sel ? 1 : 0; ma.adaptive = adaptive ? 1 : 0;
-        ma.rows_mut = e->rows_mut; ma.zbuf = nullptr; ma.pre = nullptr;
-        ma.cmrows = crs[hk]; ma.gmrows = gm_rows(h); ma.wt = h->d_wt;
-        ma.lik[0] = h->h_model.lik[0]; ma.lik[1] = h->h_model.lik[1];
-        ma.n_steps = rc->n_mh_steps; ma.store_history = h->cfg.store_history; ma.has_other = h->h_model.has_other_priors;
-        ma.alpha = rc->alpha; ma.n_parts = (double)h->cfg.n_parts;
-        ma.hist_W = h->d_hist_W; ma.hist_ld = h->n; ma.rec = h->rec; ma.debug = dbg;
+        const Mut2Args ma = mut_args(h, n_first, sel ? 1 : 0, crs[hk]);
         Seg3Args sa{};
         sa.n_first = n_first; sa.n_last = n_last; sa.enter_mut = enter_mut ? 1 : 0; sa.mrows = mrs[hk]; sa.sched = h->d_sched;
         sa.clear_status = (enter_mut && n_first == force_sel && status_pending) ? 1 : 0;
@@ -585,7 +582,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         sa.prof_stage = e->prof_stage;
         sa.gprof = sa.prof ? e->d_prof : nullptr;            // (the wall-clock stamps of every block: absolute PROF2_* offsets)
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (profile && sa.done_out) { hipEventCreate(&e0); hipEventCreate(&e1); evs3.push_back(e0); evs3.push_back(e1); hipEventRecord(e0, h->stream); }
+        if (profile && sa.done_out) { HIP_TRY(evs3.event(&e0)); HIP_TRY(evs3.event(&e1)); hipEventRecord(e0, h->stream); }       // (pair k belongs to launch k)
         // (the stage counters of all launches of a run are cleared once, in front of its first segment: a fill per launch was 5 µs each)
         if (sa.done_out && seg_launches == 0) HIP_TRY(hipMemsetAsync(e->d_done3, 0, SEG3_MAX_LAUNCHES * sizeof(int), h->stream));
 #define SMCMI_CALL(D) launch_k3_segment<D>(h, ma, sa, rc->n_blocks, rc->alpha == 1.0, shift_lag)
@@ -628,30 +625,23 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         return 0;
     };
     // a stage up to (not including) its mutation: what runs as launches in front of a segment that enters at the mutation
-    auto enq_stage_front = [&](int n, bool cert, int P, bool sel) -> int {
+    // cert: certificate passes instead of a predicted ϕ_n (adaptive schedules only); helper: K1's extra block (enq_K1)
+    auto enq_stage_front = [&](int n, bool cert, int P, bool sel, bool helper = false) -> int {
         if (cert) {
             if (int e = enq_begin(n)) return e;
             if (int e = enq_passes(n, 0, P)) return e;
-            if (int e = enq_K1(n, 1, 0)) return e;
-        } else if (!inker) {
+            if (int e = enq_K1(n, 1, 0, helper)) return e;
+        } else if (!inker) {               // many blocks per CU: the stage-begin logic once, by one block
             if (int e = enq_begin(n, adaptive ? 1 : 0)) return e;
-            if (int e = enq_K1(n, 1, 0)) return e;
+            if (int e = enq_K1(n, 1, 0, helper)) return e;
         } else if (int e = enq_K1(n, 0, adaptive ? 1 : 0)) return e;
         if (sel) { if (int e = enq_select(n)) return e; }
         return 0;
     };
-    // a whole stage; cert: certificate passes instead of a predicted ϕ_n (adaptive schedules only)
+    // a whole stage
     // next_begin: what the mutation launch's helper block runs for stage n + 1 (-1: nothing - the batch ends here, or its mode is not known)
     auto enq_stage = [&](int n, bool cert, int P, bool sel, int next_begin = -1) -> int {
-        if (cert) {
-            if (int e = enq_begin(n)) return e;
-            if (int e = enq_passes(n, 0, P)) return e;
-            if (int e = enq_K1(n, 1, 0, !sel)) return e;
-        } else if (!inker) {               // many blocks per CU: the stage-begin logic once, by one block
-            if (int e = enq_begin(n, adaptive ? 1 : 0)) return e;
-            if (int e = enq_K1(n, 1, 0, !sel)) return e;
-        } else if (int e = enq_K1(n, 0, adaptive ? 1 : 0)) return e;
-        if (sel) { if (int e = enq_select(n)) return e; }
+        if (int e = enq_stage_front(n, cert, P, sel, !sel)) return e;
         return enq_K2(n, sel ? 1 : 0, next_begin);
     };
     auto read_ctl = [&](Ctl2 *c) -> int {
@@ -698,22 +688,26 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     // (with predictions switched off every stage is four launches and a one-stage segment: a stage that runs out of solver passes idles all of
     // them behind it - short batches there, doubling while nothing stalls: 100 000 particles, n_para 1, 29 adaptive stages 7.3 -> 2.7 ms)
     int cert_sync = 8;
-    const int solver_passes = rc->solver_passes >= 1 ? rc->solver_passes : DEFAULT_SOLVER_PASSES;
-    const int first_passes = std::max(solver_passes, FIRST_SOLVER_PASSES);
-    const double N_tot = (double)h0->cfg.n_parts, thr = rc->threshold_ratio * N_tot;
+    const int first_passes = std::max(rc->solver_passes >= 1 ? rc->solver_passes : DEFAULT_SOLVER_PASSES, FIRST_SOLVER_PASSES);
+    const double N_tot = (double)h0->cfg.n_parts;
     const int sel_mode = sw().no_select_predict;   // development only
     const bool predict_select = adaptive && sel_mode != 1;
     // predicted ϕ_n needs the solver's objective to be the correction's ESS (no prior weight, quirk Q4) and a tolerance to verify against
     const bool spec_ok = adaptive && !sw().no_predictor && rc->tempered_update_prior_weight == 0.0 && !(rc->phi_rtol < 0.0);
-    bool spec_on = spec_ok;
-    int last_spec_stall = -100, spec_strikes = 0, last_solver_stall = -100;
-    int dyn_P = solver_passes;
-    if (rc->solver_passes < 1 && rc->tempering_target < 0.95) dyn_P = 2;
-    double pred_ess = cont ? h0->h_st.ess_prev : (rc->initial_ess > 0.0 ? rc->initial_ess : N_tot);
-    int pred_rl = cont ? h0->h_st.resampled_last : 0;
-    int stall_stage = -1, stall_p = 0, stages_left_est = 1 << 30;
+    stagepolicy::StallBook book(first_passes, stagepolicy::starting_passes(rc->solver_passes, DEFAULT_SOLVER_PASSES, rc->tempering_target), 8, base, spec_ok);
+    stagepolicy::Forecast forecast(rc->tempering_target, N_tot, rc->threshold_ratio * N_tot, cont ? h0->h_st.ess_prev : (rc->initial_ess > 0.0 ? rc->initial_ess : N_tot),
+                                   cont ? h0->h_st.resampled_last : 0);
+    stagepolicy::StagesLeft left;
     int launched = 0;
-    res->solver_stalls = 0; res->select_stalls = 0; res->spec_stalls = 0; res->shift_fallback_stage = 0;
+    const StallReport stall_report{res, book}; res->shift_fallback_stage = 0;
+    // mailbox, after a stall at stage sn: the posts that were actually made - stage sn - 1's mutation rows; stage sn's correction rows if only
+    // its selection is missing
+    auto mb_rewind = [&](int sn, bool cm_stands) {
+        const auto it = mb_mut_at.find(sn - 1);
+        mb_live[1] = it != mb_mut_at.end();
+        if (mb_live[1]) mb_cnt[1] = it->second;
+        if (cm_stands) { mb_cnt[0] = mb_cm_at[sn]; mb_live[0] = true; }
+    };
     Ctl2 c{};
     const auto t0 = std::chrono::steady_clock::now();
     bool finished = false;
@@ -725,8 +719,8 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     bool last_stalled = false;
     while (!finished) {
         const int room = max_iter - launched;
-        const bool to_room = whole_run_batches && spec_on && !last_stalled && force_sel < 0;
-        const int batch = adaptive && !to_room ? std::min(std::min(spec_on || !spec_ok ? cur_sync : std::min(cur_sync, cert_sync), std::max(stages_left_est, 4)), room) : room;
+        const bool to_room = whole_run_batches && book.spec_on && !last_stalled && force_sel < 0;
+        const int batch = adaptive && !to_room ? left.batch(book.spec_on || !spec_ok ? cur_sync : std::min(cur_sync, cert_sync), room) : room;
         bool stalled = false;
         int seg_a = -1, seg_b = -1;                      // pending segment of engine 3
         bool seg_enter = false, seg_sel = false;         // ... which enters at the mutation of its first stage (corrected / resampled by launches)
@@ -739,20 +733,14 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         for (int b = 0; b < batch; ++b) {
             const int n = base + launched + 2;
             bool sel = true;
-            if (predict_select) {
-                // ESS this stage will end at (helpers.jl:14-20), with a margin: a wrong "resample" guess only costs two idle launches
-                const double ess_bar = rc->tempering_target * (pred_rl ? N_tot : pred_ess);
-                const bool rs = ess_bar < thr * (1.0 + 1e-6);
-                sel = rs && sel_mode != 2;
-                pred_ess = ess_bar; pred_rl = rs ? 1 : 0;
-            }
+            if (predict_select) sel = forecast.step() && sel_mode != 2;
             // stages that follow a resample or have no mutation rows yet (first stage of a run / a continuation) get certificate
             // passes; so does everything once predictions have stopped verifying
             // (resample stages run on the predicted, verified ϕ_n like every other stage since round 4: 10.16 -> 10.00 ms on config 2)
-            const bool cert = adaptive && (!spec_on || launched < 2);
+            const bool cert = adaptive && (!book.spec_on || launched < 2);
             // engine 3 takes every stage that is expected to need neither (fixed schedules: nobody can tell which stage resamples -
             // the segment leaves at the first one that must, code 6, and the host runs that stage through the launches) ...
-            if (n == force_sel) { sel = true; if (predict_select) pred_rl = 1; }        // (a segment left at this stage: it must resample)
+            if (n == force_sel) { sel = true; if (predict_select) forecast.pred_rl = 1; }        // (a segment left at this stage: it must resample)
             if (e3 && !cert && (!sel || !adaptive || sel_inside) && n != force_sel) {
                 if (seg_a < 0) { seg_a = n; seg_enter = false; seg_sel = false; }
                 seg_b = n;
@@ -763,17 +751,17 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             // ... and the MUTATION of the others: their solver passes, correction and selection run as launches, then a new segment
             // enters at the mutation (what K2 would do) and goes on with the stages behind it
             if (e3) {
-                if (int e = enq_stage_front(n, cert, launched < 2 ? first_passes : dyn_P, sel)) return e;
+                if (int e = enq_stage_front(n, cert, book.fresh(launched), sel)) return e;
                 seg_a = seg_b = n; seg_enter = true; seg_sel = sel;
             } else {
                 // large shards: the mutation launch's helper block runs the NEXT stage's begin - in the mode that stage will be enqueued in
                 // (the same rules one stage ahead; the last stage of a batch leaves it to a launch: the sync in between may change the mode)
                 int next_begin = -1;
                 if (bighelp && b + 1 < batch) {
-                    const bool cert2 = adaptive && (!spec_on || launched + 1 < 2);
+                    const bool cert2 = adaptive && (!book.spec_on || launched + 1 < 2);
                     next_begin = cert2 ? 0 : (adaptive ? 1 : 0);
                 }
-                if (int e = enq_stage(n, cert, launched < 2 ? first_passes : dyn_P, sel, next_begin)) return e;
+                if (int e = enq_stage(n, cert, book.fresh(launched), sel, next_begin)) return e;
             }
             ++launched;
         }
@@ -789,17 +777,10 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             stalled = true;
             // mailbox: a resumed stage posts under fresh tags into tables a slower handle may still be polling for the stalled
             // stage's - every handle must have left the stalled batch first
-            if (mbox) {
-                if (int e = g.barrier()) return e;
-                // the posts that were actually made: stage sn - 1's mutation rows; stage sn's correction rows if only its selection is missing
-                const auto it = mb_mut_at.find(sn - 1);
-                mb_live[1] = it != mb_mut_at.end();
-                if (mb_live[1]) mb_cnt[1] = it->second;
-                if (code == 3) { mb_cnt[0] = mb_cm_at[sn]; mb_live[0] = true; }
-            }
-            for (int &s : ev_stage) if (s >= sn) s = -1;           // the stalled stage's mutation launch and everything behind it were no-ops
+            if (mbox) { if (int e = g.barrier()) return e; mb_rewind(sn, code == 3); }
+            evs.void_from(sn);
             prepared_stage = begun_stage = -1;                     // (nothing a helper block was enqueued for stands: the resumed stage runs on launches)
-            const bool resume_in_segment = code == 6 && e3 && !(adaptive && !spec_on);
+            const bool resume_in_segment = code == 6 && e3 && !(adaptive && !book.spec_on);
             if (!resume_in_segment) { if (int e = clear_status()) return e; }
             if (resume_in_segment) {
                 // a segment of engine 3 left at this stage (it must resample): nothing of the stage is committed.  The next batch starts
@@ -808,43 +789,32 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
                 // every one of them: 9.2 -> 8.6 ms for 300 fixed stages at N = 1e5)
                 force_sel = sn;
                 status_pending = true;                             // (the entering segment clears the status: no fill launch in front of the stage)
-                res->select_stalls += 1;
+                book.select_stall();
                 launched = sn - 2 - base;                          // (stage sn itself is the next one to enqueue)
                 c.status.code = 0;
                 break;
             } else if (code == 6) {
                 // ... with certificate passes (predictions switched off): the full path runs it
-                const bool cert6 = adaptive && !spec_on;
+                const bool cert6 = adaptive && !book.spec_on;
                 if (int e = enq_stage(sn, cert6, first_passes, true)) return e;
-                if (cert6) { stall_stage = sn; stall_p = first_passes; }
-                res->select_stalls += 1;
+                if (cert6) book.rerun(sn);
+                book.select_stall();
             } else if (code == 4) {
-                // predicted ϕ_n unusable or not verified: nothing of the stage is committed; run it through the certificate path
+                // (no usable prediction, or not verified) through the certificate path
                 if (int e = enq_stage(sn, true, first_passes, true)) return e;
-                stall_stage = sn; stall_p = first_passes;
-                res->spec_stalls += 1;
-                if (sn - last_spec_stall <= 4) { if (++spec_strikes >= 2) spec_on = false; }
-                else spec_strikes = 0;
-                last_spec_stall = sn;
+                book.spec_stall(sn);
             } else if (code == 2) {
-                const int had = (sn == stall_stage) ? stall_p : (sn - base <= 3 ? first_passes : dyn_P);
-                const int more = 8;
-                // (a bracketing search halves its interval at least every pass: 1100 passes exhaust the exponent range of a double - whatever
-                // keeps a stage asking for more is not a search any more, and the host must not feed it for ever)
-                if (had > 1200) return set_err(SMCMI_ERR_BRACKET, "adaptive tempering solver: the search for phi_n does not terminate (the ESS objective is not a number?)");
-                if (int e = enq_passes(sn, had, had + more)) return e;
+                const auto more = book.solver_stall(sn);
+                if (!more.ok) return bracket_error();
+                if (int e = enq_passes(sn, more.p0, more.p1)) return e;
                 if (int e = enq_K1(sn, 1, 0)) return e;
                 if (int e = enq_select(sn)) return e;
                 if (int e = enq_K2(sn, 1)) return e;
-                stall_stage = sn; stall_p = had + more;
-                res->solver_stalls += 1;
-                if (sn - last_solver_stall <= 4 && dyn_P < 4) ++dyn_P;
-                last_solver_stall = sn;
             } else {
-                // the stage must resample but its selection kernels were not enqueued: run the rest of it
+                // (code 3: only its selection is missing) the rest of it
                 if (int e = enq_select(sn)) return e;
                 if (int e = enq_K2(sn, 1)) return e;
-                res->select_stalls += 1;
+                book.select_stall();
             }
             launched = sn - 1 - base;
             if (int e = read_ctl(&c)) return e;
@@ -856,14 +826,14 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             const int sn = c.status.stage;
             shift_lag = false;
             res->shift_fallback_stage = sn;
-            if (mbox) { if (int e = g.barrier()) return e; const auto it = mb_mut_at.find(sn - 1); mb_live[1] = it != mb_mut_at.end(); if (mb_live[1]) mb_cnt[1] = it->second; }
+            if (mbox) { if (int e = g.barrier()) return e; mb_rewind(sn, false); }
             for (auto *h : g.hs) {
                 HIP_TRY(hipSetDevice(h->cfg.device));
                 h->h_lag0 = 0;
                 HIP_TRY(hipMemcpyAsync(&h->d_st->rp.shift_lag, &h->h_lag0, sizeof(int), hipMemcpyHostToDevice, h->stream));
                 HIP_TRY(hipMemsetAsync(&h->e2->d_ctl->status, 0, 4 * sizeof(int), h->stream));      // code, stage, err, pad
             }
-            for (int &s : ev_stage) if (s >= sn) s = -1;
+            evs.void_from(sn);
             prepared_stage = begun_stage = -1;
             force_sel = -1; status_pending = false;
             launched = sn - 2 - base;
@@ -880,14 +850,11 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             finished = true;
             break;
         }
-        if (c.bg.stage == p.stage && c.bg.phi_n > c.bg.phi_prev && p.phi_n < 1.0) {
-            const double left = (1.0 - p.phi_n) / (c.bg.phi_n - c.bg.phi_prev);
-            stages_left_est = left < 1e6 ? (int)left + 1 : 1 << 30;
-        }
-        if (predict_select) { pred_ess = p.ess; pred_rl = p.do_resample; }
+        if (c.bg.stage == p.stage) left.observe(p.phi_n, c.bg.phi_n - c.bg.phi_prev);
+        if (predict_select) forecast.anchor(p.ess, p.do_resample);
         last_stalled = stalled;
         if (rc->sync_every <= 0) cur_sync = stalled ? sync_every : std::min(2 * cur_sync, 4 * sync_every);
-        if (!spec_on && spec_ok) cert_sync = stalled ? 8 : std::min(2 * cert_sync, sync_every);
+        if (!book.spec_on && spec_ok) cert_sync = stalled ? 8 : std::min(2 * cert_sync, sync_every);
     }
     // (a batch that ended with a segment's exit note was read before the launch had finished: everything behind this line reads what it left)
     HIP_TRY(hipSetDevice(h0->cfg.device));
@@ -901,20 +868,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     }
     const auto t1 = std::chrono::steady_clock::now();
     const DevState &s = h0->h_st;
-    res->kernel_ms_mutate = 0.0; res->n_mutate_launches = 0;
-    if (profile && !evs.empty()) {
-        // event pairs bracket dispatch + kernel: calibrate the fixed part around an empty kernel of the same grid (smcmi_run)
-        HIP_TRY(hipSetDevice(h0->cfg.device));
-        const double over = event_overhead_ms(h0);
-        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
-            float ms = 0.f;
-            if (ev_stage[k / 2] >= 0 && ev_stage[k / 2] <= s.stage && hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) {
-                res->kernel_ms_mutate += std::max(0.0, (double)ms - over);
-                res->n_mutate_launches += 1;
-            }
-        }
-    }
-    for (hipEvent_t e : evs) hipEventDestroy(e);
+    if (int e = evs.tally(h0, s.stage + 1, res)) return e;
     // segments of engine 3: launches, the stages they completed and (profile mode) their HIP-event time
     res->n_segments = seg_launches; res->segment_stages = 0; res->kernel_ms_segments = 0.0;
     // (workers + gatherers; no gatherer where the workers take each other's rows: launch2.hpp launch_k3_seg)
@@ -927,13 +881,12 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         HIP_TRY(hipMemcpy(done.data(), h0->e2->d_done3, sizeof(int) * nl, hipMemcpyDeviceToHost));
         for (int k = 0; k < nl; ++k) res->segment_stages += done[k];
         int timed_stages = 0;
-        for (size_t k = 0; k + 1 < evs3.size(); k += 2) {
+        for (size_t k = 0; k + 1 < evs3.events.size(); k += 2) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, evs3[k], evs3[k + 1]) == hipSuccess) { res->kernel_ms_segments += (double)ms; timed_stages += done[k / 2]; }
+            if (hipEventElapsedTime(&ms, evs3.events[k], evs3.events[k + 1]) == hipSuccess) { res->kernel_ms_segments += (double)ms; timed_stages += done[k / 2]; }
         }
-        if (!evs3.empty()) res->segment_stages = timed_stages;        // (profile mode: the stages behind kernel_ms_segments)
+        if (!evs3.events.empty()) res->segment_stages = timed_stages;        // (profile mode: the stages behind kernel_ms_segments)
     }
-    for (hipEvent_t e : evs3) hipEventDestroy(e);
     finish_result(res, s, t0, t1);
     if (mbox) {
         // a hand-over that timed out poisoned the sums with NaN: report THAT, not the NaN-ESS message the poisoned sums lead to

@@ -1,7 +1,9 @@
 // runsetup.hpp - how a run starts and ends, once: argument checks, schedule, RunParams, the fresh or continued DevState, the stage-1 records
-// and history columns, the result fill and the event-overhead calibration.  Plain functions the four drivers call (smcmi_run, run_callback,
-// run_sharded_impl, run2_impl); their stage loops stay with them.  Included by smcmi.hip in front of run1.hpp.
+// and history columns, the result fill, and the profile events with their overhead calibration.  What the four drivers share around their
+// stage loops (run1_impl, run_callback, run_sharded_impl, run2_impl); what they decide between stages is in stagepolicy.hpp.  Included by
+// smcmi.hip in front of run1.hpp.
 #pragma once
+#include "stagepolicy.hpp"
 
 static int check_run_config(const smcmi_handle *h, const smcmi_run_config *rc) {
     const int nf = h->h_model.n_free;
@@ -89,12 +91,14 @@ static int finish_error(const DevState &s) {
     if (!s.done) return set_err(SMCMI_ERR_CAPACITY, "max_stages exceeded before the tempering schedule reached 1");
     return 0;
 }
+static int bracket_error() { return set_err(SMCMI_ERR_BRACKET, "adaptive tempering solver: the search for phi_n does not terminate (the ESS objective is not a number?)"); }
 // An event pair brackets [previous kernel done -> this kernel done]: dispatch of the kernel included.  Calibrate that fixed part with pairs
 // around an empty kernel of the mutation kernel's grid (its predecessor of comparable size) and subtract it, so the figure is the kernel's
 // own duration (what rocprofv3 --kernel-trace reports).
 static double event_overhead_ms(smcmi_handle *h) {
-    hipEvent_t c0, c1;
-    hipEventCreate(&c0); hipEventCreate(&c1);
+    devmem::Handles made;
+    hipEvent_t c0 = nullptr, c1 = nullptr;
+    if (made.event(&c0) != hipSuccess || made.event(&c1) != hipSuccess) return 0.0;
     double acc_ms = 0.0;
     int got = 0;
     for (int r = 0; r < 64; ++r) {
@@ -106,7 +110,43 @@ static double event_overhead_ms(smcmi_handle *h) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, c0, c1) == hipSuccess) { acc_ms += ms; ++got; }
     }
-    hipEventDestroy(c0); hipEventDestroy(c1);
     // an empty kernel of this grid itself lasts ~2.5 µs in a rocprofv3 kernel trace (wave launch + drain): leave that in
     return got ? std::max(0.0, acc_ms / got - 0.0025) : 0.0;
 }
+// Profile mode (use_graph == 2: direct launches with HIP events around the mutation kernel): the event pairs of a run, each tagged with the
+// stage or iteration it belongs to; destroyed on every return.
+struct MutationEvents {
+    bool on;
+    explicit MutationEvents(bool profile) : on(profile) {}
+    // a pair for a launch of stage / iteration `tag` (off, or no event to be had: two nulls - the launch goes untimed)
+    void pair(int tag, hipEvent_t *e0, hipEvent_t *e1) {
+        *e0 = *e1 = nullptr;
+        if (!on) return;
+        hipEvent_t a = nullptr, b = nullptr;
+        if (made_.event(&a) != hipSuccess || made_.event(&b) != hipSuccess) return;
+        pairs_.push_back({a, b, tag});
+        *e0 = a; *e1 = b;
+    }
+    // a stage stalled: its mutation launch and everything behind it were no-ops
+    void void_from(int tag) { for (Pair &p : pairs_) if (p.tag >= tag) p.tag = -1; }
+    // kernel_ms_mutate / n_mutate_launches from the pairs that stand with a tag below `bound` (the stages the run completed), each minus the
+    // calibrated overhead
+    int tally(smcmi_handle *h, int bound, smcmi_result *res) const {
+        res->kernel_ms_mutate = 0.0; res->n_mutate_launches = 0;
+        if (pairs_.empty()) return 0;
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        const double over = event_overhead_ms(h);
+        for (const Pair &p : pairs_) {
+            float ms = 0.f;
+            if (p.tag >= 0 && p.tag < bound && hipEventElapsedTime(&ms, p.e0, p.e1) == hipSuccess) { res->kernel_ms_mutate += std::max(0.0, (double)ms - over); res->n_mutate_launches += 1; }
+        }
+        return 0;
+    }
+private:
+    struct Pair { hipEvent_t e0, e1; int tag; };
+    devmem::Handles made_;
+    std::vector<Pair> pairs_;
+};
+// the stalls a run's book counted (stagepolicy.hpp); StallReport: they reach the result on every return, an early one included
+static void put_stalls(smcmi_result *res, const stagepolicy::StallBook &b) { res->solver_stalls = b.solver_stalls; res->select_stalls = b.select_stalls; res->spec_stalls = b.spec_stalls; }
+struct StallReport { smcmi_result *res; const stagepolicy::StallBook &book; ~StallReport() { put_stalls(res, book); } };

@@ -418,27 +418,51 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
         for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); HIP_TRY(hipMemsetAsync(h->d_tot_acc, 0, sizeof(double) * (ES + MAX_SHARDS), h->stream)); }
     }
     // One stage = the single-GPU launch sequence with the collectives in-stream.  Nothing in it needs the host: on an adaptive
-    // schedule resampling is predictable (smcmi_run), so the selection path - all-gather of weights and shard clouds, global
-    // scan, gather - is enqueued exactly where a resample is expected (its kernels gate themselves on the device's decision)
-    // and elsewhere k_moments_reg takes the post-correction decision itself; a wrong expectation or a solver that runs out
-    // of passes stalls the run (done = 3 / 2) identically on every rank and is resumed at the next host sync.  Fixed schedules
-    // cannot be predicted: they keep one flag read per stage.
-    // mode 0: full stage with selection path; 1: no selection expected; 2: tail only (from k_post_correct on; selection path)
-    // spec: predict -> correct -> verify (no certificate pass, no all-reduce for it: 2 collectives per stage);
-    // skip_begin: resume of such a stage through the certificate path
+    // schedule the selection path - all-gather of weights and shard clouds, global scan, gather - is enqueued exactly where a
+    // resample is forecast (stagepolicy.hpp; its kernels gate themselves on the device's decision) and elsewhere k_moments_reg
+    // takes the post-correction decision itself; a wrong expectation or a solver that runs out of passes stalls the run
+    // (done = 3 / 2) identically on every rank and is resumed at the next host sync.  Fixed schedules cannot be predicted: they
+    // keep one flag read per stage.
     // use_graph == 2: HIP events around the first local shard's mutation launches (the `roofline` figure of a multi-GPU bench line)
-    const bool profile = rc->use_graph == 2;
-    devmem::Handles prof_evs;              // (destroyed on every return)
-    std::vector<hipEvent_t> &mut_evs = prof_evs.events;
-    auto enqueue = [&](int p0, int P, int mode, bool spec = false, bool skip_begin = false) -> int {
-        if (spec) P = 0;
+    MutationEvents evs(rc->use_graph == 2);
+    // the global cumulative weights on every shard, from the all-gathered weight column
+    auto scan_full = [&](smcmi_handle *h) {
+        CloudPtrs wcl{};
+        wcl.buf[0] = wcl.buf[1] = h->d_full_w; wcl.n = h->cfg.n_parts; wcl.R = 1;
+        k_weight_chunk_sums<<<h->nb_full, TB, 0, h->stream>>>(wcl, h->d_st, h->d_part_full);
+        k_chunk_offsets<<<1, 1, 0, h->stream>>>(h->d_st, h->d_part_full, h->nb_full, h->d_off_full, 0.0, 0);
+        k_scan_weights<<<h->nb_full, TB, 0, h->stream>>>(wcl, h->d_st, h->d_off_full, h->d_cum_full, 0, h->nb_full);
+    };
+    auto gather_full = [&](smcmi_handle *h) {
+        const long long N = h->cfg.n_parts;
+        k_resample_gather<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_cum_full, N, h->cfg.gid0, N, rc->resampling_method,
+                                                                                h->cfg.seed, 0u, nullptr, h->d_anc, h->d_full_cloud, 0, h->n, 1);
+    };
+    // proposal set-up from the all-reduced moments, the mutation, and what the next begin reads of it totalled over all shards
+    auto mutate_and_reduce = [&](int prep_mode, int fin_slot) -> int {
+        for (auto *h : g.hs) {
+            HIP_TRY(hipSetDevice(h->cfg.device));
+            launch_prepare_in_run(h, h->d_tot_mom, 1, prep_mode, fin_slot);
+            hipEvent_t pe0 = nullptr, pe1 = nullptr;
+            if (h == h0) { evs.pair(0, &pe0, &pe1); if (pe0) hipEventRecord(pe0, h->stream); }
+            const int nbl = launch_mutate(h, rc->n_blocks, 0, rc->alpha);
+            if (pe1) hipEventRecord(pe1, h->stream);
+            if (predict) k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_esum_part, nbl, ES, h->d_tot_acc, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
+            else k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_acc_part, nbl, 1, h->d_tot_acc + EACC, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
+        }
+        if (predict) return g.allreduce([](smcmi_handle *h) { return h->d_tot_acc; }, ES + g.world);
+        return g.allreduce([](smcmi_handle *h) { return h->d_tot_acc + EACC; }, 1 + g.world);
+    };
+    // q (run1.hpp StageReq): passes p0 .. p0 + passes - 1; spec: no certificate pass, no all-reduce for it - 2 collectives per stage
+    auto enqueue = [&](const StageReq &q) -> int {
+        const int p0 = q.p0, P = q.spec ? 0 : p0 + q.passes;
         const int fin_slot = P == 0 ? 0 : (P & 1);
         // no selection expected + register kernels: the correction pass gathers the moments too, so (ΣW̃, ΣW̃², pair sums) travel
         // in ONE all-reduce (3 collectives per stage instead of 4); k_prepare_mutation decides, the mutation kernel normalises
-        const bool cm = mode == 1 && can_fuse_cm(h0);
+        const bool cm = q.no_select && can_fuse_cm(h0);
         const int npf = h0->npairs + 2;
-        for (auto *h : g.hs) { h->fused_cm = cm; h->spec_stage = spec && cm; }
-        if (mode == 2) {
+        for (auto *h : g.hs) { h->fused_cm = cm; h->spec_stage = q.spec && cm; }
+        if (q.tail_only) {
             // resume of a stalled stage: its correction left the per-block (ΣW̃, ΣW̃²) partials - total them first
             for (auto *h : g.hs) {
                 HIP_TRY(hipSetDevice(h->cfg.device));
@@ -446,8 +470,8 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             }
             if (int rc2 = g.allreduce([](smcmi_handle *h) { return h->d_tot_fin; }, 2)) return rc2;
         }
-        if (mode != 2) {
-            if (p0 == 0 && !skip_begin)
+        if (!q.tail_only) {
+            if (p0 == 0 && !q.skip_begin)
                 for (auto *h : g.hs) {
                     HIP_TRY(hipSetDevice(h->cfg.device));
                     h->run_adaptive = predict;
@@ -478,22 +502,8 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
                 if (int rc2 = g.allreduce([](smcmi_handle *h) { return h->d_tot_fin; }, 2)) return rc2;
             }
         }
-        if (cm) {
-            for (auto *h : g.hs) {
-                HIP_TRY(hipSetDevice(h->cfg.device));
-                launch_prepare_in_run(h, h->d_tot_mom, 1, 3, fin_slot);
-                hipEvent_t pe0 = nullptr, pe1 = nullptr;
-                if (profile && h == h0) { prof_evs.event(&pe0); prof_evs.event(&pe1); hipEventRecord(pe0, h->stream); }
-                const int nbl = launch_mutate(h, rc->n_blocks, 0, rc->alpha);
-                if (pe1) hipEventRecord(pe1, h->stream);
-                if (predict) k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_esum_part, nbl, ES, h->d_tot_acc, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
-                else k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_acc_part, nbl, 1, h->d_tot_acc + EACC, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
-            }
-            if (predict) { if (int rc2 = g.allreduce([](smcmi_handle *h) { return h->d_tot_acc; }, ES + g.world)) return rc2; }
-            else if (int rc2 = g.allreduce([](smcmi_handle *h) { return h->d_tot_acc + EACC; }, 1 + g.world)) return rc2;
-            return 0;
-        }
-        if (mode == 1) {
+        if (cm) return mutate_and_reduce(3, fin_slot);
+        if (q.no_select) {
             for (auto *h : g.hs) {
                 HIP_TRY(hipSetDevice(h->cfg.device));
                 // the moments kernel decides from the all-reduced (ΣW̃, ΣW̃²) handed over as the partials of one block
@@ -524,21 +534,18 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             // resample redistribution: all-to-all-v of exactly the rows each shard's slots descend from (systematic resampling; the
             // default), or an all-gather of the whole cloud (multinomial resampling, or SMCMI_RESAMPLE_EXCHANGE=allgather)
             const bool a2a = rs && !sw().resample_allgather && rc->resampling_method == SMCMI_RESAMPLE_SYSTEMATIC && g.world > 1;
-            if (rs && a2a) {
-                // all-to-all-v redistribution: weights are all-gathered (N doubles), every shard forms the global cumulative sum and
-                // the ancestor range of every shard's slots; then only the rows inside a shard's range travel to it
-                const size_t nloc = (size_t)h0->n;
+            const size_t nloc = (size_t)h0->n;
+            if (rs) {                                      // either way the weights are all-gathered (N doubles)
                 if (int rc2 = g.allgather([](smcmi_handle *h) { return (const double *)(h->cl.buf[0] + (long long)(h->R - 1) * h->n); },
                                           [](smcmi_handle *h) { return h->d_full_w; }, nloc)) return rc2;
+            }
+            if (a2a) {
+                // all-to-all-v redistribution: every shard forms the global cumulative sum and the ancestor range of every shard's slots;
+                // then only the rows inside a shard's range travel to it
                 for (auto *h : g.hs) {
                     HIP_TRY(hipSetDevice(h->cfg.device));
-                    const long long N = h->cfg.n_parts;
-                    CloudPtrs wcl{};
-                    wcl.buf[0] = wcl.buf[1] = h->d_full_w; wcl.n = N; wcl.R = 1;
-                    k_weight_chunk_sums<<<h->nb_full, TB, 0, h->stream>>>(wcl, h->d_st, h->d_part_full);
-                    k_chunk_offsets<<<1, 1, 0, h->stream>>>(h->d_st, h->d_part_full, h->nb_full, h->d_off_full, 0.0, 0);
-                    k_scan_weights<<<h->nb_full, TB, 0, h->stream>>>(wcl, h->d_st, h->d_off_full, h->d_cum_full, 0, h->nb_full);
-                    k_anc_ranges<<<1, 64, 0, h->stream>>>(h->d_st, h->d_cum_full, N, h->n, g.world, h->cfg.seed, h->d_anc);
+                    scan_full(h);
+                    k_anc_ranges<<<1, 64, 0, h->stream>>>(h->d_st, h->d_cum_full, h->cfg.n_parts, h->n, g.world, h->cfg.seed, h->d_anc);
                 }
                 std::vector<long long> ranges(2 * (size_t)g.world);
                 HIP_TRY(hipSetDevice(h0->cfg.device));
@@ -546,32 +553,12 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
                 HIP_TRY(hipStreamSynchronize(h0->stream));
                 if (ranges[0] >= 0) {                      // -1: the device decided not to resample after all
                     if (int rc2 = g.exchange_rows(ranges)) return rc2;
-                    for (auto *h : g.hs) {
-                        HIP_TRY(hipSetDevice(h->cfg.device));
-                        const long long N = h->cfg.n_parts;
-                        k_resample_gather<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_cum_full, N, h->cfg.gid0, N,
-                                                                                                rc->resampling_method, h->cfg.seed, 0u, nullptr, h->d_anc,
-                                                                                                h->d_full_cloud, 0, h->n, 1);
-                    }
+                    for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); gather_full(h); }
                 }
             } else if (rs) {
-                const size_t nloc = (size_t)h0->n;
-                if (int rc2 = g.allgather([](smcmi_handle *h) { return (const double *)(h->cl.buf[0] + (long long)(h->R - 1) * h->n); },
-                                          [](smcmi_handle *h) { return h->d_full_w; }, nloc)) return rc2;
                 if (int rc2 = g.allgather([](smcmi_handle *h) { return (const double *)h->cl.buf[0]; },
                                           [](smcmi_handle *h) { return h->d_full_cloud; }, nloc * h0->R)) return rc2;
-                for (auto *h : g.hs) {
-                    HIP_TRY(hipSetDevice(h->cfg.device));
-                    const long long N = h->cfg.n_parts;
-                    CloudPtrs wcl{};
-                    wcl.buf[0] = wcl.buf[1] = h->d_full_w; wcl.n = N; wcl.R = 1;
-                    k_weight_chunk_sums<<<h->nb_full, TB, 0, h->stream>>>(wcl, h->d_st, h->d_part_full);
-                    k_chunk_offsets<<<1, 1, 0, h->stream>>>(h->d_st, h->d_part_full, h->nb_full, h->d_off_full, 0.0, 0);
-                    k_scan_weights<<<h->nb_full, TB, 0, h->stream>>>(wcl, h->d_st, h->d_off_full, h->d_cum_full, 0, h->nb_full);
-                    k_resample_gather<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_cum_full, N, h->cfg.gid0, N,
-                                                                                            rc->resampling_method, h->cfg.seed, 0u, nullptr, h->d_anc,
-                                                                                            h->d_full_cloud, 0, h->n, 1);
-                }
+                for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); scan_full(h); gather_full(h); }
             }
             for (auto *h : g.hs) {
                 HIP_TRY(hipSetDevice(h->cfg.device));
@@ -611,19 +598,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             if (failed != 0.0) return set_err(SMCMI_ERR_CALLBACK, "the likelihood callback failed on another rank of the sharded run");
             return 0;
         }
-        for (auto *h : g.hs) {
-            HIP_TRY(hipSetDevice(h->cfg.device));
-            launch_prepare_in_run(h, h->d_tot_mom, 1, 2);
-            hipEvent_t pe0 = nullptr, pe1 = nullptr;
-            if (profile && h == h0) { prof_evs.event(&pe0); prof_evs.event(&pe1); hipEventRecord(pe0, h->stream); }
-            const int nbl = launch_mutate(h, rc->n_blocks, 0, rc->alpha);
-            if (pe1) hipEventRecord(pe1, h->stream);
-            if (predict) k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_esum_part, nbl, ES, h->d_tot_acc, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
-            else k_reduce_partials<<<1, TB, 0, h->stream>>>(h->d_acc_part, nbl, 1, h->d_tot_acc + EACC, h->d_emax_part, nbl, h->d_tot_acc + ES, shard_rank(h), g.world);
-        }
-        if (predict) { if (int rc2 = g.allreduce([](smcmi_handle *h) { return h->d_tot_acc; }, ES + g.world)) return rc2; }
-        else if (int rc2 = g.allreduce([](smcmi_handle *h) { return h->d_tot_acc + EACC; }, 1 + g.world)) return rc2;
-        return 0;
+        return mutate_and_reduce(2, 0);
     };
 
     const auto t0 = std::chrono::steady_clock::now();
@@ -631,32 +606,25 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     const int base = cont ? h0->h_st.stage - 1 : 0;      // stages completed before this call
     const int max_iter = (adaptive ? h0->cfg.max_stages : rc->n_phi - 1) - base;
     const int sync_every = rc->sync_every > 0 ? rc->sync_every : 16;
-    const int first_passes = std::max(P_default, FIRST_SOLVER_PASSES);
-    const double N_tot = (double)h0->cfg.n_parts, thr = rc->threshold_ratio * N_tot;
-    double pred_ess = cont ? h0->h_st.ess_prev : (rc->initial_ess > 0.0 ? rc->initial_ess : N_tot);
-    int pred_rl = cont ? h0->h_st.resampled_last : 0, stall_stage = -1, stall_p = 0;
-    int done = 0, iters = 0, stalls = 0, sel_stalls = 0, spec_stalls = 0;
+    const double N_tot = (double)h0->cfg.n_parts;
+    stagepolicy::Forecast forecast(rc->tempering_target, N_tot, rc->threshold_ratio * N_tot, cont ? h0->h_st.ess_prev : (rc->initial_ess > 0.0 ? rc->initial_ess : N_tot),
+                                   cont ? h0->h_st.resampled_last : 0);
+    int done = 0, iters = 0;
     const bool spec_ok = predict_select && predict && can_fuse_cm(h0) &&
                          rc->tempered_update_prior_weight == 0.0 && !(rc->phi_rtol < 0.0);
-    bool spec_on = spec_ok;                   // switched off after repeated verification failures (see smcmi_run)
-    int last_spec_stall = -100, spec_strikes = 0, last_solver_stall = -100;
-    int dyn_P = P_default;                    // raised when stages keep running out of passes
-    int stages_left_est = 1 << 30;            // (1 - ϕ_n) / (ϕ_n - ϕ_{n-1}) at the last sync (smcmi_run)
+    stagepolicy::StallBook book(std::max(P_default, FIRST_SOLVER_PASSES), P_default, 4, base, spec_ok);
+    stagepolicy::StagesLeft left;
     while (iters < max_iter && !done) {
-        const int batch = host_mut ? 1 : (adaptive ? std::min(std::min(sync_every, std::max(stages_left_est, 4)), max_iter - iters) : max_iter - iters);
+        const int batch = host_mut ? 1 : (adaptive ? left.batch(sync_every, max_iter - iters) : max_iter - iters);
         for (int b = 0; b < batch; ++b) {
-            int mode = 0;
-            if (predict_select) {
-                const double ess_bar = rc->tempering_target * (pred_rl ? N_tot : pred_ess);
-                const bool rs = ess_bar < thr * (1.0 + 1e-6);
-                mode = (!rs || sel_mode == 2) ? 1 : 0;
-                pred_ess = ess_bar; pred_rl = rs ? 1 : 0;
-            }
-            const bool spec = spec_on && mode == 1 && iters >= 2;
-            if (int rc2 = enqueue(0, adaptive ? (iters < 2 ? first_passes : dyn_P) : 0, mode, spec)) return rc2;
+            StageReq q;
+            if (predict_select) q.no_select = !forecast.step() || sel_mode == 2;
+            q.spec = book.spec_on && q.no_select && iters >= 2;
+            q.passes = adaptive ? book.fresh(iters) : 0;
+            if (int rc2 = enqueue(q)) return rc2;
             ++iters;
         }
-        // one 64-byte copy per sync: done flag, resample flag and ESS of the last stage are contiguous in DevState (smcmi_run)
+        // one 64-byte copy per sync: done flag, resample flag and ESS of the last stage are contiguous in DevState
         DevState head;
         constexpr size_t head_off = offsetof(DevState, stage), head_len = offsetof(DevState, ess) - offsetof(DevState, stage);
         for (;;) {
@@ -668,42 +636,24 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
             // stall (identical on every rank: all decisions come from all-reduced totals): clear it and resume that stage
             if (pull_state(h0)) return SMCMI_ERR_HIP;
             const int st_i = h0->h_st.stage;
-            const int had = (st_i == stall_stage) ? stall_p : (st_i - base <= 3 ? first_passes : dyn_P);
             for (auto *h : g.hs) {
                 HIP_TRY(hipSetDevice(h->cfg.device));
                 const int zero = 0;
                 HIP_TRY(hipMemcpyAsync(&h->d_st->done, &zero, sizeof(int), hipMemcpyHostToDevice, h->stream));
             }
-            if (done == 4) {
-                // a stage without certificate pass had no usable / verified prediction: nothing is committed, redo it in full
+            if (done == 4)
                 for (auto *h : g.hs) {
                     HIP_TRY(hipSetDevice(h->cfg.device));
                     k_solver_rearm<<<1, 64, 0, h->stream>>>(h->d_st, h->d_sched);
                 }
-                if (int rc2 = enqueue(0, first_passes, 0, false, true)) return rc2;
-                stall_stage = st_i; stall_p = first_passes;
-                ++spec_stalls;
-                if (st_i - last_spec_stall <= 4) { if (++spec_strikes >= 2) spec_on = false; }
-                else spec_strikes = 0;
-                last_spec_stall = st_i;
-            } else if (done == 2) {
-                if (int rc2 = enqueue(had, had + 4, 0)) return rc2;
-                stall_stage = st_i; stall_p = had + 4;
-                ++stalls;
-                if (st_i - last_solver_stall <= 4 && dyn_P < 4) ++dyn_P;
-                last_solver_stall = st_i;
-            } else {
-                if (int rc2 = enqueue(had, had, 2)) return rc2;
-                ++sel_stalls;
-            }
+            StageReq q;
+            if (!resume_request(book, done, st_i, &q)) return bracket_error();
+            if (int rc2 = enqueue(q)) return rc2;
             iters = st_i - 1 - base;
         }
-        if (!done && head.phi_n >= 1.0) break;      // the last stage of the batch reached ϕ = 1: the closing k_stage_begin finishes (smcmi_run)
-        if (head.phi_n > head.phi_prev && head.phi_n < 1.0) {
-            const double left = (1.0 - head.phi_n) / (head.phi_n - head.phi_prev);
-            stages_left_est = left < 1e6 ? (int)left + 1 : 1 << 30;
-        }
-        if (predict_select) { pred_rl = head.resampled_last; pred_ess = head.ess_prev; }    // (the copy that ended the loop above)
+        if (!done && head.phi_n >= 1.0) break;      // the last stage of the batch reached ϕ = 1: the closing k_stage_begin finishes
+        left.observe(head.phi_n, head.phi_n - head.phi_prev);
+        if (predict_select) forecast.anchor(head.ess_prev, head.resampled_last);    // (the copy that ended the loop above)
     }
     // fold the last acceptance rate, close the run
     for (auto *h : g.hs) {
@@ -716,16 +666,8 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     const DevState &s = h0->h_st;
     memset(res, 0, sizeof(*res));
     finish_result(res, s, t0, t1);
-    res->solver_stalls = stalls; res->select_stalls = sel_stalls; res->spec_stalls = spec_stalls;
-    if (!mut_evs.empty()) {
-        // event pairs bracket dispatch + kernel; launches of stalled (no-op) stages are short and rare - they stay in the mean.
-        // The dispatch part is calibrated like in smcmi_run: pairs around an empty kernel of the same grid, minus its own ~2.5 µs.
-        HIP_TRY(hipSetDevice(h0->cfg.device));
-        const double over = event_overhead_ms(h0);
-        for (size_t k = 0; k + 1 < mut_evs.size(); k += 2) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, mut_evs[k], mut_evs[k + 1]) == hipSuccess) { res->kernel_ms_mutate += std::max(0.0, (double)ms - over); res->n_mutate_launches += 1; }
-        }
-    }
+    put_stalls(res, book);
+    // (launches of stalled - no-op - stages are short and rare: they stay in the mean)
+    if (int e = evs.tally(h0, 1, res)) return e;
     return finish_error(s);
 }

@@ -188,7 +188,8 @@ def test_switches_hpp_is_the_only_reader_of_the_environment_and_matches_the_desi
 
 def test_devmem_hpp_is_the_only_caller_of_the_allocators():
     """csrc/devmem.hpp owns every device and pinned allocation: the runtime's five allocator and free calls occur there and nowhere else
-    under csrc/ (a buffer allocated beside the owner is one nothing gives back on an error path)."""
+    under csrc/ (a buffer allocated beside the owner is one nothing gives back on an error path).  So do the event constructors; the stall
+    rules' state occurs in csrc/stagepolicy.hpp alone; and no call of enqueue_stage passes a bare true / false."""
     csrc = os.path.join(ROOT, "smc.jl_amd", "csrc")
     calls = ("hipMalloc", "hipExtMallocWithFlags", "hipHostMalloc", "hipFree", "hipHostFree")
     pat = re.compile(r"\b(%s)\b" % "|".join(calls))
@@ -197,6 +198,16 @@ def test_devmem_hpp_is_the_only_caller_of_the_allocators():
     others = {f: sorted(v) for f, v in found.items() if v}
     assert not others, others
     assert len(found) > 20, sorted(found)
+    # likewise the events (devmem.hpp Handles destroys what it made on every return), and the stall rules live in stagepolicy.hpp alone
+    src = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))}
+    assert [f for f, t in src.items() if "hipEventCreate" in t] == ["devmem.hpp"]
+    for word in ("spec_strikes", "last_solver_stall"):
+        assert [f for f, t in src.items() if word in t] == ["stagepolicy.hpp"], word
+    # ... and a stage is requested by named fields: no call of enqueue_stage carries a bare true / false
+    calls = [m.group(0) for t in src.values() for m in re.finditer(r"\benqueue_stage\s*\(([^;{]*)\)\s*;", t)]
+    assert len(calls) >= 4, calls
+    bare = [c for c in calls if any(a.strip() in ("true", "false") for a in re.split(r"[(),]", c))]
+    assert not bare, bare
 
 
 def test_the_owner_gives_everything_back_under_fault_injection(tmp_path):
@@ -213,3 +224,19 @@ def test_the_owner_gives_everything_back_under_fault_injection(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stderr == "", r.stderr
+
+
+def test_stage_policy_states_the_rules_the_drivers_had(tmp_path):
+    """tests/policy_check.cpp drives csrc/stagepolicy.hpp - the resample forecast, the stall book, the stages-left estimate and batch bound the
+    host drivers share - with plain numbers against the rules as the drivers' own copies stated them; host code under AddressSanitizer and
+    UBSan, no HIP: exit status 0 and nothing on stderr."""
+    import subprocess
+
+    exe = tmp_path / "policy_check"
+    r = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "policy_check.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip() == "ok" and r.stderr == "", r.stdout + r.stderr
