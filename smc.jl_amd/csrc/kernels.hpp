@@ -29,6 +29,13 @@ namespace smcmi {
 
 constexpr int TB = 256;  // threads per block for streaming kernels (4 wavefronts)
 
+// a member of a kernel's dynamic LDS where its layout (ldslayout.hpp) places it: OFF = layout[member], a compile-time constant, or
+// the same at run time for the kernels whose n_para is a launch value
+template <class T, size_t OFF>
+__device__ __forceinline__ T *lds_at(double *sm) { return (T *)((char *)sm + OFF); }
+template <class T, int N>
+__device__ __forceinline__ T *lds_at(double *sm, const lds::Layout<N> &l, int id) { return (T *)((char *)sm + l[id]); }
+
 // development aid: shader-clock stamp of (block 0, thread 0) into prof[slot] when prof != nullptr
 #define SMCMI_STAMP(prof, slot)                                                                              \
     do {                                                                                                    \
@@ -1366,17 +1373,16 @@ static __global__ void k_anc_ranges(const DevState *st, const double *cum, long 
 // resample), write them to the weight column and the W history, and accumulate the augmented second-moment matrix
 // Σ w x̃ x̃ᵀ, x̃ = (1, θ - shift), from which weighted_mean / weighted_cov follow (src/particle.jl:481-483, 526-529).
 // Particles are staged through LDS in tiles so every (a,b) pair is accumulated from on-chip data.
-constexpr int MT = 256;                      // particles per LDS tile
 #ifndef SMCMI_INST_UNIT
 static __global__ void __launch_bounds__(TB) k_moments(CloudPtrs cl, DevState *st, double *partials, double *hist_W,
                                                 long long hist_ld, int standalone) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!standalone && st->done) return;
     const int d = cl.R - 5, da = d + 1, npairs = da * (da + 1) / 2;
-    const int ldx = MT + 1;                  // padded row: pair threads reading different rows hit different banks
-    double *xs = sm;                         // da rows: row 0 = 1, row a+1 = θ_a - shift_a
-    double *wv = xs + (long long)da * ldx;   // weights of the tile
-    unsigned char *pa = (unsigned char *)(wv + ldx), *pb = pa + npairs;
+    const int ldx = MT + 1;                  // padded row
+    const auto O = lds::moments(d);
+    double *xs = lds_at<double>(sm, O, lds::O_xs), *wv = lds_at<double>(sm, O, lds::O_wv);
+    unsigned char *pa = lds_at<unsigned char>(sm, O, lds::O_pa), *pb = lds_at<unsigned char>(sm, O, lds::O_pb);
     for (int p = threadIdx.x; p < npairs; p += TB) {   // decode pair index -> (a <= b)
         int a = 0, rem = p;
         while (rem >= da - a) { rem -= da - a; ++a; }
@@ -1897,11 +1903,9 @@ static __global__ void __launch_bounds__(PT) k_prepare_mutation(DevState *st, co
     __shared__ int s_fail;
     if (!standalone && st->done) return;
     const int d = md->d, nf = md->n_free, t = threadIdx.x, da = d + 1, npairs = da * (da + 1) / 2;
-    double *tot = psm;                       // [npairs] (rounded up to 64)
-    double *covl = tot + ((npairs + 63) / 64) * 64;   // [d*d]
-    double *sig_f = covl + d * d;            // [nf*nf]
-    double *A = sig_f + nf * nf;             // [nf*nf] scaled block covariance
-    double *Ls = A + nf * nf;                // [nf*nf] factor of the current block
+    const auto O = lds::prep(d, nf);
+    double *tot = lds_at<double>(psm, O, lds::P_tot), *covl = lds_at<double>(psm, O, lds::P_covl), *sig_f = lds_at<double>(psm, O, lds::P_sigf);
+    double *A = lds_at<double>(psm, O, lds::P_A), *Ls = lds_at<double>(psm, O, lds::P_Ls);
     if (t == 0) s_fail = 0;
     if (t < nf) fi[t] = md->free_inds[t];
     double c = st->c;
@@ -2146,17 +2150,15 @@ struct MutArgs {
 
 // LS = 4 (lgss_kalman family only, MODE 0): FOUR lanes per particle - a 256-thread block carries 64 particles, the four lanes of a
 // quad run the per-particle part (draw, densities, prior, decision) redundantly on the same values (same counters -> same random
-// numbers; nothing to exchange) and share the Kalman filter (model.hpp kalman_lgss_quad).  Per wavefront: θ, θ' [d][16], then
-// {draw, solve scratch [d][16]} overlaid with the filter's 16 transposition slots (dead while the filter runs: the accepted
-// proposal is copied from θ').  Lane 0 of a quad stores the particle and feeds the block sums.
-// what the proposal of the lane-split kernel reads per block and per parameter, staged in LDS once per launch (in DevState / ModelDev
-// they are global loads inside rolled loops: a dependent ~0.3-1 µs round trip per iteration with one wavefront per SIMD)
-struct MutStage {
-    double L[13 * 13], mu_b[13], sd_draw[13], sd_dens[13], logdet[13], lo[13], hi[13], prior_a[13], prior_b[13], prior_k[13];
-    int block_ptr[14], blocks_all[13], l_off[13], fixed[13], prior_family[13];
-};
-constexpr int mutate_wave_bytes_ls4(int d) {
-    return (2 * d * 16 * 8 + ((2 * d * 16 * 8 > 16 * KALMAN4_SLOT_BYTES) ? 2 * d * 16 * 8 : 16 * KALMAN4_SLOT_BYTES) + 15) / 16 * 16;
+// numbers; nothing to exchange) and share the Kalman filter (model.hpp kalman_lgss_quad).  Lane 0 of a quad stores the particle and
+// feeds the block sums.  (The per-wavefront vectors: ldslayout.hpp mut_cols; the staged proposal constants: MutStage.)
+// The per-particle vectors of this thread's particle (LS = 4: of its wavefront) from the start `gen` of the block's vectors
+struct MutColPtrs { double *th, *tn, *y, *v; };
+template <int LS>
+__device__ __forceinline__ MutColPtrs mut_col_ptrs(double *gen, int d, int T) {
+    double *wave_base = LS == 4 ? gen + (long long)(threadIdx.x >> 6) * (lds::mutate_wave_bytes_ls4(lds::LS4_D) / 8) : gen;
+    const auto C = lds::mut_cols(d, T, LS);
+    return {lds_at<double>(wave_base, C, lds::C_th), lds_at<double>(wave_base, C, lds::C_tn), lds_at<double>(wave_base, C, lds::C_y), lds_at<double>(wave_base, C, lds::C_v)};
 }
 // The Metropolis-Hastings moves of ONE particle (src/mutation.jl:56-138; mixture draw helpers.jl:87-100, proposal densities :128-164,
 // bounds, log-prior, device likelihood) for any n_para, with the per-particle vectors in LDS columns th / tn / y / v ([k][T], column tid):
@@ -2383,12 +2385,8 @@ __global__ void __launch_bounds__(256, 1) k_mutate(CloudPtrs cl, const DevState 
     const int quad_lane = threadIdx.x & 3;
     const bool lead = (LS == 1) || quad_lane == 0;
     const int d = md->d, nf = md->n_free;
-    double *wave_base = (LS == 4) ? sm + (long long)(threadIdx.x >> 6) * (mutate_wave_bytes_ls4(13) / 8) : sm;
-    double *th = wave_base;                // current θ           [d][T]
-    double *tn = th + (long long)d * T;    // proposed θ          [d][T]
-    double *y = tn + (long long)d * T;     // z / draw            [d][T]
-    double *v = y + (long long)d * T;      // triangular-solve scratch [d][T]
-    double *red = (LS == 4) ? sm + (long long)(blockDim.x >> 6) * (mutate_wave_bytes_ls4(13) / 8) : v + (long long)d * T;    // [blockDim.x/64]
+    const MutColPtrs cp = mut_col_ptrs<LS>(sm, d, T);
+    double *th = cp.th, *tn = cp.tn, *y = cp.y, *v = cp.v;
     const long long i = (LS == 4) ? (long long)blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2) : (long long)blockIdx.x * T + tid;
     const bool live = i < cl.n;
     constexpr int src = 0;
@@ -2399,7 +2397,9 @@ __global__ void __launch_bounds__(256, 1) k_mutate(CloudPtrs cl, const DevState 
     double like = 0.0, lprior = 0.0, like_prev = 0.0, accept = 0.0;
     // LS = 1: the same staging when the host reserved the room (MODE 0, n_para <= 13: ma.stage_consts)
     const bool staged = (LS == 4) || (MODE == 0 && ma.stage_consts && d <= 13);
-    MutStage *S = staged ? (MutStage *)(red + 8) : nullptr;
+    const auto O = lds::mutate(d, T, LS, staged);
+    double *red = lds_at<double>(sm, O, lds::G_red);
+    MutStage *S = staged ? lds_at<MutStage>(sm, O, lds::G_stage) : nullptr;
     if (staged) {
         for (int e = threadIdx.x; e < d * d; e += blockDim.x) S->L[e] = st->L[e];
         if ((int)threadIdx.x < d) {
@@ -2728,20 +2728,14 @@ SMCMI_FP_CONTRACT
         if (profme) { unsigned long long tt_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt_)::"memory"); profp[slot] = (long long)tt_; } \
     } while (0)
     SMCMI_PROF(0);
-    double *Ls = sm;                                // [D*D] row-major with stride D, identity-padded
-    double *mu_s = Ls + D * D;                      // [D]
-    double *sdd_s = mu_s + D, *sdn_s = sdd_s + D;   // [D] each
-    double *red = sdn_s + D;                        // [4]
-    double *m_lo = red + 4;
-    double *m_hi = m_lo + D, *m_a = m_hi + D, *m_b = m_a + D, *m_k = m_b + D;
-    double *l_par = m_k + D;                        // [2 * LIK_PAR_MAX]
-    double *l_dat = l_par + 2 * LIK_PAR_MAX;        // [LIK_LDS_CAP]
-    double *Lraw = l_dat + LIK_LDS_CAP;             // [D*D] packed block factors as k_prepare_mutation wrote them
-    double *logdet_s = Lraw + D * D;                // [D]
-    double *mub_raw = logdet_s + D, *sdd_raw = mub_raw + D, *sdn_raw = sdd_raw + D;   // [D] each, block order
-    int *ball_s = (int *)(sdn_raw + D);             // [D]
-    int *m_fix = ball_s + D + (D & 1), *m_fam = m_fix + D;
-    int *bptr_s = m_fam + D, *loff_s = bptr_s + D + 1, *ball_raw = loff_s + D;
+    using namespace lds;
+    constexpr Mut2Layout O = mut2(D, 4, LIK_LDS_CAP, false);        // (the mutation body's arrays as in Mut2Lds; four wavefronts: red[4])
+    double *Ls = lds_at<double, O[M_Ls]>(sm), *red = lds_at<double, O[M_red]>(sm), *m_lo = lds_at<double, O[M_lo]>(sm), *m_hi = lds_at<double, O[M_hi]>(sm);
+    double *m_a = lds_at<double, O[M_a]>(sm), *m_b = lds_at<double, O[M_b]>(sm), *m_k = lds_at<double, O[M_k]>(sm), *l_par = lds_at<double, O[M_lpar]>(sm);
+    double *l_dat = lds_at<double, O[M_ldat]>(sm), *Lraw = lds_at<double, O[M_Lraw]>(sm), *logdet_s = lds_at<double, O[M_logdet]>(sm);
+    double *mub_raw = lds_at<double, O[M_mub]>(sm), *sdd_raw = lds_at<double, O[M_sddr]>(sm), *sdn_raw = lds_at<double, O[M_sdnr]>(sm);
+    int *m_fix = lds_at<int, O[M_fix]>(sm), *m_fam = lds_at<int, O[M_fam]>(sm), *bptr_s = lds_at<int, O[M_bptr]>(sm), *loff_s = lds_at<int, O[M_loff]>(sm);
+    int *ball_raw = lds_at<int, O[M_ballr]>(sm);
     // ---- round 1: every uniform input of the launch, issued back to back (a dependent global round trip costs ~1 µs
     // at this occupancy, so the kernel is organised as: one round of parameter loads, one round of particle loads,
     // compute, one round of stores).  nb / nf are launch arguments so the copy extents do not depend on loaded data.

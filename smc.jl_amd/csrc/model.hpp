@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "devstate.hpp"
+#include "ldslayout.hpp"
 
 namespace smcmi {
 
@@ -59,7 +60,6 @@ struct LikView {
     const double *aux;
     long long aux_rows, aux_cols;
 };
-constexpr int LIK_LDS_CAP = 768;          // doubles of likelihood data + regressors staged in LDS
 
 template <class M, class Th>
 __device__ inline bool in_bounds(const M &m, Th th) {
@@ -297,7 +297,6 @@ __device__ inline double kalman_lgss(const double *thv, const double *ydat, long
 // parameter vector pass any finite numbers and ignore the result).
 // P is not symmetrised (the asymmetric part is rounding noise that Tm contracts).  Values agree with kalman_lgss2 to ~1e-13
 // relative, not bit for bit (different summation orders).  xslot: this particle's LDS slot (KALMAN4_SLOT_BYTES, 16-byte aligned).
-constexpr int KALMAN4_SLOT_BYTES = 576;
 typedef __attribute__((address_space(3))) char *lds_bytes;
 typedef double v2f64 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) v2f64 *lds_v2f64;

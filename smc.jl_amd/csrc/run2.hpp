@@ -530,7 +530,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
                 SMCMI_D_SWITCH(d, SMCMI_CALL)
 #undef SMCMI_CALL
             } else {
-#define SMCMI_CALL(D) launch_k2_mutate<D>(h, ma, rc->n_blocks, rc->alpha == 1.0)
+#define SMCMI_CALL(D) if (int lrc = launch_k2_mutate<D>(h, ma, rc->n_blocks, rc->alpha == 1.0)) return lrc
             SMCMI_D_SWITCH(d, SMCMI_CALL)
 #undef SMCMI_CALL
             }
@@ -585,7 +585,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         if (profile && sa.done_out) { HIP_TRY(evs3.event(&e0)); HIP_TRY(evs3.event(&e1)); hipEventRecord(e0, h->stream); }       // (pair k belongs to launch k)
         // (the stage counters of all launches of a run are cleared once, in front of its first segment: a fill per launch was 5 µs each)
         if (sa.done_out && seg_launches == 0) HIP_TRY(hipMemsetAsync(e->d_done3, 0, SEG3_MAX_LAUNCHES * sizeof(int), h->stream));
-#define SMCMI_CALL(D) launch_k3_segment<D>(h, ma, sa, rc->n_blocks, rc->alpha == 1.0, shift_lag)
+#define SMCMI_CALL(D) if (int lrc = launch_k3_segment<D>(h, ma, sa, rc->n_blocks, rc->alpha == 1.0, shift_lag)) return lrc
         SMCMI_D_SWITCH(d, SMCMI_CALL)
 #undef SMCMI_CALL
         HIP_TRY(hipGetLastError());                  // (a rejected launch would otherwise surface as a bogus capacity / time-out error)

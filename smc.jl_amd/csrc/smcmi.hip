@@ -10,6 +10,8 @@
 #include "switches.hpp"
 #include "route.hpp"
 
+static constexpr size_t LS4_LDS = lds::mutate(lds::LS4_D, 16, 4, true).bytes;      // the four-lane k_mutate<0, 4>'s dynamic LDS
+
 static thread_local std::string g_err;
 extern "C" const char *smcmi_last_error(void) { return g_err.c_str(); }
 extern "C" int smcmi_version(void) { return 1; }
@@ -221,7 +223,7 @@ static int create_impl(smcmi_handle *h, const smcmi_config *cfg) {
     // mutation block size: largest of 256/128/64 threads whose per-thread LDS vectors fit 64 KiB
     for (int T : {256, 128, 64}) {
         h->mut_T = T;
-        h->mut_lds = (size_t)(4 * h->d * T + T / 64) * sizeof(double) + (h->d <= 13 ? 64 + sizeof(MutStage) : 0);   // (+ staged proposal constants)
+        h->mut_lds = lds::mutate(h->d, T, 1, h->d <= 13).bytes;      // (n_para <= 13: with the staged proposal constants)
         if (h->mut_lds <= 64 * 1024) break;
     }
     h->nb_mut = (int)((n + h->mut_T - 1) / h->mut_T);
@@ -231,9 +233,9 @@ static int create_impl(smcmi_handle *h, const smcmi_config *cfg) {
     // 64-thread blocks, which spread the wavefronts evenly: 60.7 / 61.0 / 61.1 µs per launch, no difference - the kernel is not bound by its slowest CU)
     h->reg_T = 256;
     h->nb_reg = (int)((n + h->reg_T - 1) / h->reg_T);
-    h->mom_lds = (size_t)((h->d + 2) * (MT + 1)) * sizeof(double) + 2 * (size_t)h->npairs + 16;
+    h->mom_lds = lds::moments(h->d).bytes;
     h->comm_cap = std::max<long long>(2 * KC, h->npairs) + 8;
-    h->prep_lds = (size_t)(((h->npairs + 63) / 64) * 64 + 4 * h->d * h->d + 8) * sizeof(double);
+    h->prep_lds = lds::prep(h->d, h->d).bytes;
     if (dmalloc(h->mem, &h->d_part_ess[0], (size_t)h->nb_e * 2 * KC) || dmalloc(h->mem, &h->d_part_ess[1], (size_t)h->nb_e * 2 * KC) || dmalloc(h->mem, &h->d_part_fin, (size_t)h->nb_e * 2) || dmalloc(h->mem, &h->d_part_cm, (size_t)h->nb_e * (h->npairs + 2)) || dmalloc(h->mem, &h->d_prep_rows, (size_t)PREP_G * PT + 8) || dmalloc(h->mem, &h->d_wt, n) ||
         dmalloc(h->mem, &h->d_chunk_off, h->nb_e) || dmalloc(h->mem, &h->d_cum, n) || dmalloc(h->mem, &h->d_anc, n) ||
         dmalloc(h->mem, &h->d_part_mom, (size_t)std::max(h->nb_m, h->nb_mr) * h->npairs) || dmalloc(h->mem, &h->d_totals, h->npairs) ||
@@ -263,7 +265,7 @@ static int create_impl(smcmi_handle *h, const smcmi_config *cfg) {
     HIP_TRY(hipFuncSetAttribute((const void *)k_moments, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mom_lds));
     HIP_TRY(hipFuncSetAttribute((const void *)k_prepare_mutation, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->prep_lds));
     HIP_TRY(hipFuncSetAttribute((const void *)k_mutate<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mut_lds));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_mutate<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * mutate_wave_bytes_ls4(13) + 64 + sizeof(MutStage))));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_mutate<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LS4_LDS));
     HIP_TRY(hipFuncSetAttribute((const void *)k_mutate<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mut_lds));
     HIP_TRY(hipFuncSetAttribute((const void *)k_mutate<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mut_lds));
     if (set_mutate_attrs(h)) return SMCMI_ERR_HIP;
@@ -796,9 +798,7 @@ static int stage_blocks(smcmi_handle *h, const double *mu_free, const double *Si
 }
 
 // ---- mutation launch: register-resident kernel for models with n_para <= 10, generic LDS kernel beyond
-static size_t reg_lds_bytes(int D) {
-    return (size_t)(2 * D * D + 12 * D + 4 + 2 * LIK_PAR_MAX + LIK_LDS_CAP) * sizeof(double) + (size_t)(6 * D + 8) * sizeof(int) + 32;
-}
+static constexpr size_t reg_lds_bytes(int D) { return lds::mut2(D, 4, LIK_LDS_CAP, false).bytes; }    // (k_mutate_reg: the mutation body's arrays with red of 4)
 template <int D>
 static void launch_reg(smcmi_handle *h, const MutArgs &ma, int standalone) {
     if (h->launch_alpha1)
@@ -859,7 +859,7 @@ static int launch_mutate(smcmi_handle *h, int n_blocks, int standalone, double a
     case 10: launch_reg<10>(h, ma, standalone); break;
     default:
         if (use_ls4_mutate(h)) {
-            k_mutate<0, 4><<<h->nb_mut_ls4, 256, 4 * mutate_wave_bytes_ls4(13) + 64 + sizeof(MutStage), h->stream>>>(h->cl, h->d_st, h->d_model, ma,
+            k_mutate<0, 4><<<h->nb_mut_ls4, 256, LS4_LDS, h->stream>>>(h->cl, h->d_st, h->d_model, ma,
                                                                                                              h->d_acc_part, standalone);
             return h->nb_mut_ls4;
         }

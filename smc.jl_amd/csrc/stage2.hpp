@@ -30,12 +30,9 @@
 
 namespace smcmi {
 
-constexpr int V2_MAXV = 8;        // virtual shards
-constexpr int RMUT = 34;          // mutation row: ES = 32 sums (energy power sums | Σ accept), [32] = energy maximum, [33] unused
+// (V2_MAXV virtual shards, RMUT doubles per mutation row, GRP rows per canonical reduction group, pad2: ldslayout.hpp)
 constexpr int RMAX_IDX = 32;
 constexpr int T1 = 512;           // threads of a correction block
-constexpr int GRP = 64;           // rows per canonical reduction group
-constexpr int pad2(int m) { return (m + 1) & ~1; }   // row widths are even: rows are totalled with 16-byte loads (pad column = 0)
 
 // development aid (SMCMI_PROF2=<stage>): ONE layout of the handle's stamp buffer (Eng2::d_prof, long long), so that no two users share a slot
 // whatever mix of launches and segments the profiled stage runs through:
@@ -1022,7 +1019,7 @@ __device__ inline void k2_cm_row_one(double v, const double (&xx)[D + 1], bool l
 // Prop2Glob for the mutation launch: k2_prepare without its launch, its kernel start and its launch boundary.
 struct Prop2Glob;
 struct Prep2Args {
-    int enable;                   // the launch carries the helper block (block Vl * nb1; dynamic LDS = k2_lds_bytes)
+    int enable;                   // the launch carries the helper block (block Vl * nb1; dynamic LDS = Mut2Lds's layout, lds::mut2)
     int nb, nf;                   // random blocks / free parameters
     unsigned long long seed;
     Rows2 cmrows;                 // this launch's correction totals as the mailbox delivers them
@@ -1761,38 +1758,35 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
     return *s_fail == 0;
 }
 
-// LDS arrays of k2_mutate (the mutation's, as in k_mutate_reg, then the prologue's scratch)
+// LDS arrays of k2_mutate (ldslayout.hpp mut2: the mutation's, as in k_mutate_reg, then the prologue's scratch)
 template <int D>
 struct Mut2Lds {
     static constexpr int DA = D + 1, NP = DA * (DA + 1) / 2, NPF = NP + 2;
-    double *Ls, *mu_s, *sdd_s, *sdn_s, *red, *m_lo, *m_hi, *m_a, *m_b, *m_k, *l_par, *l_dat, *Lraw, *logdet_s, *mub_raw, *sdd_raw, *sdn_raw;
-    int *ball_s, *m_fix, *m_fam, *bptr_s, *loff_s, *ball_raw;
+    double *Ls, *red, *m_lo, *m_hi, *m_a, *m_b, *m_k, *l_par, *l_dat, *Lraw, *logdet_s, *mub_raw, *sdd_raw, *sdn_raw;
+    int *m_fix, *m_fam, *bptr_s, *loff_s, *ball_raw;
     double *s_vt, *s_tot, *covl, *sig_f, *Aw, *Lw, *mean_s, *mu_f;
     int *bfree, *fi, *fi_j;
-    // lik_cap: doubles reserved for staged likelihood data (the generic mutation body of n_para > 10 reads its data where it is: 0)
-    __device__ explicit Mut2Lds(double *sm, int lik_cap = LIK_LDS_CAP) {
-        Ls = sm; mu_s = Ls + D * D; sdd_s = mu_s + D; sdn_s = sdd_s + D; red = sdn_s + D;
-        m_lo = red + 8; m_hi = m_lo + D; m_a = m_hi + D; m_b = m_a + D; m_k = m_b + D;
-        l_par = m_k + D; l_dat = l_par + 2 * LIK_PAR_MAX; Lraw = l_dat + lik_cap; logdet_s = Lraw + D * D;
-        mub_raw = logdet_s + D; sdd_raw = mub_raw + D; sdn_raw = sdd_raw + D;
-        ball_s = (int *)(sdn_raw + D); m_fix = ball_s + D + (D & 1); m_fam = m_fix + D;
-        bptr_s = m_fam + D; loff_s = bptr_s + D + 1; ball_raw = loff_s + D;
-        s_vt = (double *)(((uintptr_t)(ball_raw + D + 1) + 15) & ~(uintptr_t)15);
-        s_tot = s_vt + V2_MAXV * pad2(NPF);
-        covl = s_tot + pad2(NPF) + 4; sig_f = covl + D * D; Aw = sig_f + D * D; Lw = Aw + D * D;
-        mean_s = Lw + D * D; mu_f = mean_s + D;
-        bfree = (int *)(mu_f + D); fi = bfree + D; fi_j = fi + D;
+    // lik_data = false: no room for staged likelihood data (the generic mutation body of n_para > 10 reads its data where it is)
+    __device__ explicit Mut2Lds(double *sm, bool lik_data = true) {
+        if (lik_data) place<LIK_LDS_CAP>(sm); else place<0>(sm);
+    }
+    template <int CAP>
+    __device__ void place(double *sm) {
+        using namespace lds;
+        constexpr Mut2Layout O = mut2(D, 8, CAP);
+        Ls = lds_at<double, O[M_Ls]>(sm); red = lds_at<double, O[M_red]>(sm);
+        m_lo = lds_at<double, O[M_lo]>(sm); m_hi = lds_at<double, O[M_hi]>(sm); m_a = lds_at<double, O[M_a]>(sm); m_b = lds_at<double, O[M_b]>(sm);
+        m_k = lds_at<double, O[M_k]>(sm); l_par = lds_at<double, O[M_lpar]>(sm); l_dat = lds_at<double, O[M_ldat]>(sm); Lraw = lds_at<double, O[M_Lraw]>(sm);
+        logdet_s = lds_at<double, O[M_logdet]>(sm); mub_raw = lds_at<double, O[M_mub]>(sm); sdd_raw = lds_at<double, O[M_sddr]>(sm);
+        sdn_raw = lds_at<double, O[M_sdnr]>(sm);
+        m_fix = lds_at<int, O[M_fix]>(sm); m_fam = lds_at<int, O[M_fam]>(sm); bptr_s = lds_at<int, O[M_bptr]>(sm);
+        loff_s = lds_at<int, O[M_loff]>(sm); ball_raw = lds_at<int, O[M_ballr]>(sm);
+        s_vt = lds_at<double, O[M_svt]>(sm); s_tot = lds_at<double, O[M_stot]>(sm);
+        covl = lds_at<double, O[M_covl]>(sm); sig_f = lds_at<double, O[M_sigf]>(sm); Aw = lds_at<double, O[M_Aw]>(sm); Lw = lds_at<double, O[M_Lw]>(sm);
+        mean_s = lds_at<double, O[M_mean]>(sm); mu_f = lds_at<double, O[M_muf]>(sm);
+        bfree = lds_at<int, O[M_bfree]>(sm); fi = lds_at<int, O[M_fi]>(sm); fi_j = lds_at<int, O[M_fij]>(sm);
     }
 };
-// ... of the mutation body alone (Ls .. ball_raw: what a kernel that loads a finished proposal needs - k2b_mutate, stage2b.hpp)
-constexpr size_t k2_lds_bytes_body(int D, int lik_cap = LIK_LDS_CAP) {
-    return (size_t)(2 * D * D + 12 * D + 8 + 2 * LIK_PAR_MAX + lik_cap) * sizeof(double) + (size_t)(6 * D + 8) * sizeof(int) + 32;
-}
-constexpr size_t k2_lds_bytes(int D, int lik_cap = LIK_LDS_CAP) {
-    const size_t np = (size_t)(D + 1) * (D + 2) / 2, npf = np + 2;
-    return (size_t)(2 * D * D + 12 * D + 8 + 2 * LIK_PAR_MAX + lik_cap) * sizeof(double) + (size_t)(6 * D + 8) * sizeof(int) + 32 +
-           (V2_MAXV * (npf + 1) + npf + 5 + 4 * D * D + 2 * D) * sizeof(double) + (size_t)(3 * D + 4) * sizeof(int) + 32;
-}
 
 struct Mut2Stage {             // what the prologue hands to the mutation body (LDS)
     Begin2 bg;
@@ -2188,29 +2182,25 @@ SMCMI_FP_CONTRACT
 // and shares the filter (model.hpp kalman_lgss_quad).  One mutation row per block (never paired), totalled per virtual shard by the last
 // block to finish (Tail2): with global particle ids in the RNG the results do not depend on the number of handles, bit for bit.
 // Replaces, for these models, engine 1's eight-launch stage (src/smc_main.jl:427-484 as k_post_correct ... k_mutate) by K1 -> K2.
-constexpr size_t k2w_lds_bytes(int D, int LS) {
-    const size_t pro = (k2_lds_bytes(D, 0) + 15) / 16 * 16;
-    return pro + (LS == 4 ? (size_t)4 * mutate_wave_bytes_ls4(13) : (size_t)4 * D * 256 * sizeof(double)) + 64;
-}
 template <int D, int LS>
 __global__ void __launch_bounds__(256, 1) k2w_mutate(CloudPtrs cl, DevState *st, Ctl2 *ctl, const ModelDev *md, Geo2 g, Mut2Args ma, int nb, int nf) {
     static_assert(LS == 1 || (LS == 4 && D == 13), "four lanes per particle: the lgss_kalman family (13 parameters)");
     constexpr int TB2 = 256, P = LS == 4 ? 64 : 256;           // threads / particles of a block
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ Mut2Stage S;
-    const Mut2Lds<D> L(sm, 0);
+    const Mut2Lds<D> L(sm, false);
     const int n = ma.n;
     int rs = 0;
     if (!k2_prologue<D, TB2>(st, ctl, md, ma, L, &S, nb, nf, &rs)) return;
     const double phi_n = S.bg.phi_n, e_center = S.bg.e_center, nrm_sumw = L.s_tot[0], nrm_N = ma.n_parts;
     // ---- the per-particle LDS vectors behind the prologue's area
-    double *gen = sm + (k2_lds_bytes(D, 0) + 15) / 16 * 2;
+    double *gen = lds_at<double, lds::k2w(D, LS)[lds::W_cols]>(sm);
     const int T = LS == 4 ? 16 : TB2;                                                // stride of the per-particle vectors
     const int tid = LS == 4 ? (((int)threadIdx.x & 63) >> 2) : (int)threadIdx.x;     // column in them
     const int quad_lane = threadIdx.x & 3;
     const bool lead = LS == 1 || quad_lane == 0;
-    double *wave_base = LS == 4 ? gen + (long long)(threadIdx.x >> 6) * (mutate_wave_bytes_ls4(13) / 8) : gen;
-    double *th = wave_base, *tn = th + (long long)D * T, *y = tn + (long long)D * T, *v = y + (long long)D * T;
+    const MutColPtrs cp = mut_col_ptrs<LS>(gen, D, T);
+    double *th = cp.th, *tn = cp.tn, *y = cp.y, *v = cp.v;
     const int vl = (int)blockIdx.x / g.nb2, r = (int)blockIdx.x % g.nb2;
     long long beg, end;
     vchunk(g, vl, r, P, beg, end);
@@ -2249,21 +2239,28 @@ __global__ void __launch_bounds__(256, 1) k2w_mutate(CloudPtrs cl, DevState *st,
     if (blockIdx.x == 0) k2_bookkeeping<D, TB2>(st, ctl, ma, L, &S, rs);
 }
 
+// The finished proposal of stage n and its decision, from the prologue's LDS into Prop2Glob (T threads)
+template <int D, int T>
+__device__ __forceinline__ void k2_store_proposal(Prop2Glob *out, const Mut2Lds<D> &L, const Mut2Stage &S, int nb, int nf, int rs, int n) {
+    const int tid = threadIdx.x;
+    for (int e = tid; e < nf * nf; e += T) out->Lraw[e] = L.Lraw[e];
+    for (int e = tid; e < nf; e += T) { out->mub[e] = L.mub_raw[e]; out->sdd[e] = L.sdd_raw[e]; out->sdn[e] = L.sdn_raw[e]; out->ball[e] = L.ball_raw[e]; }
+    for (int b = tid; b < nb; b += T) { out->loff[b] = L.loff_s[b]; out->logdet[b] = L.logdet_s[b]; }
+    for (int b = tid; b <= nb; b += T) out->bptr[b] = L.bptr_s[b];
+    if (tid == 0) { out->rs = rs; out->s1 = L.s_tot[0]; out->phi_n = S.bg.phi_n; out->e_center = S.bg.e_center; out->go = 1; out->stage = n; }
+}
+
 // Decision, bookkeeping and proposal of stage n by one block (large clouds, sharded runs): K2's prologue as its own launch.
 template <int D>
 __global__ void __launch_bounds__(256) k2_prepare(DevState *st, Ctl2 *ctl, const ModelDev *md, Mut2Args ma, int nb, int nf, Prop2Glob *out) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ Mut2Stage S;
     const Mut2Lds<D> L(sm);
-    const int tid = threadIdx.x, n = ma.n;
+    const int n = ma.n;
     int rs = 0;
     ma.pre = nullptr;
     if (!k2_prologue<D, 256>(st, ctl, md, ma, L, &S, nb, nf, &rs)) return;      // (a stall leaves out->stage stale: K2 does nothing)
-    for (int e = tid; e < nf * nf; e += 256) out->Lraw[e] = L.Lraw[e];
-    for (int e = tid; e < nf; e += 256) { out->mub[e] = L.mub_raw[e]; out->sdd[e] = L.sdd_raw[e]; out->sdn[e] = L.sdn_raw[e]; out->ball[e] = L.ball_raw[e]; }
-    for (int b = tid; b < nb; b += 256) { out->loff[b] = L.loff_s[b]; out->logdet[b] = L.logdet_s[b]; }
-    for (int b = tid; b <= nb; b += 256) out->bptr[b] = L.bptr_s[b];
-    if (tid == 0) { out->rs = rs; out->s1 = L.s_tot[0]; out->phi_n = S.bg.phi_n; out->e_center = S.bg.e_center; out->go = 1; out->stage = n; }
+    k2_store_proposal<D, 256>(out, L, S, nb, nf, rs, n);
     k2_bookkeeping<D, 256>(st, ctl, ma, L, &S, rs);
 }
 
@@ -2274,18 +2271,11 @@ __device__ void k2_prepare_block(DevState *st, Ctl2 *ctl, const Prep2Args &pb, i
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ Mut2Stage S;
     const Mut2Lds<D> L(sm);
-    const int tid = threadIdx.x;
     Mut2Args ma{};
     ma.n = n; ma.seed = pb.seed; ma.cmrows = pb.cmrows; ma.sel_enqueued = 0; ma.rec = pb.rec;
     int rs = 0;
     if (!k2_prologue<D, T1>(st, ctl, pb.md, ma, L, &S, pb.nb, pb.nf, &rs, 1, true)) return;
-    Prop2Glob *out = pb.out;
-    const int nb = pb.nb, nf = pb.nf;
-    for (int e = tid; e < nf * nf; e += T1) out->Lraw[e] = L.Lraw[e];
-    for (int e = tid; e < nf; e += T1) { out->mub[e] = L.mub_raw[e]; out->sdd[e] = L.sdd_raw[e]; out->sdn[e] = L.sdn_raw[e]; out->ball[e] = L.ball_raw[e]; }
-    for (int b = tid; b < nb; b += T1) { out->loff[b] = L.loff_s[b]; out->logdet[b] = L.logdet_s[b]; }
-    for (int b = tid; b <= nb; b += T1) out->bptr[b] = L.bptr_s[b];
-    if (tid == 0) { out->rs = rs; out->s1 = L.s_tot[0]; out->phi_n = S.bg.phi_n; out->e_center = S.bg.e_center; out->go = 1; out->stage = n; }
+    k2_store_proposal<D, T1>(pb.out, L, S, pb.nb, pb.nf, rs, n);
     k2_bookkeeping<D, T1>(st, ctl, ma, L, &S, rs);
 }
 

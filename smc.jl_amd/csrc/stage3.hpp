@@ -33,7 +33,7 @@ namespace smcmi {
 #ifndef SMCMI_K3_WAVES
 #define SMCMI_K3_WAVES 2          // (launch bound: wavefronts per SIMD the segment kernel is compiled for; 2 = one 512-thread block per CU)
 #endif
-constexpr int T3 = 512;                      // threads = particles of a block
+// (T3 = 512 threads = particles of a block: ldslayout.hpp)
 constexpr int TICK3_STRIDE = 32;             // ints between ticket counters: one 128-byte line each (the arrivals of different shards do not queue behind each other)
 constexpr int SEG3_TICKS = (V2_MAXV + 1) * TICK3_STRIDE;      // per kind: one ticket counter per local virtual shard + the top one
 
@@ -408,22 +408,6 @@ static __global__ void __launch_bounds__(T3, 2) k3_census(int *tick, unsigned lo
 }
 #endif
 
-// dynamic LDS a gatherer needs for the rows of its virtual shard (at most 2 GRP = 128 of them, 72 or RMUT columns)
-constexpr size_t k3_gather_lds_bytes(int D) {
-    const size_t npf = (size_t)(D + 1) * (D + 2) / 2 + 2, mcm = npf + (npf & 1);
-    return (size_t)2 * GRP * (mcm > (size_t)RMUT ? mcm : (size_t)RMUT) * sizeof(double);
-}
-constexpr size_t k3_park_offset(int D) { return (k2_lds_bytes(D) + 15) / 16 * 2; }          // in doubles, 16-byte aligned
-// (k2's arrays | the parking area (D + 2) T3 | the particle in transit through an in-place selection: (D + 5) T3, see k3_sel_cols)
-constexpr size_t k3_lds_bytes(int D, int sel_cols = 0) {
-    return k3_park_offset(D) * sizeof(double) + (size_t)(D + 2) * T3 * sizeof(double) + (size_t)sel_cols * T3 * sizeof(double);
-}
-// columns of LDS a segment kernel gets for the particle in transit (0: the particle is parked in device memory instead, Sel3Args::transit).
-// The mixture variant carries T3 x D doubles of static z columns and the dense mixture block: with them and the D + 5 columns a block
-// outgrows a CU's 160 KB beyond n_para 7 (24 KB: a bound on the rest of the kernel's static arrays)
-constexpr int k3_sel_cols(int D, bool alpha1) {
-    return (alpha1 || 24 * 1024 + ((size_t)T3 * D + 3 * D * D + 3 * D + 2) * sizeof(double) + k3_lds_bytes(D, D + 5) <= 160 * 1024) ? D + 5 : 0;
-}
 // (MIX = false, α = 1: the mixture-component uniform is never read, so its Philox call is not made at all)
 template <int D, bool MIX = true>
 __device__ inline void k3_draw_park(double *z_park, unsigned long long seed, unsigned long long pid, unsigned stage, int db, int debug) {
@@ -925,6 +909,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     __shared__ int mixpos[ALPHA1 ? 1 : D];
     __shared__ double mixzt[ALPHA1 ? 1 : T3 * D];
     Mut2Lds<D> L(sm);
+    constexpr lds::Seg3Layout O3 = k3_layout(D, ALPHA1, CH);
     const int tid = threadIdx.x;
     constexpr int FAST = ALPHA1 ? (SMCMI_A1FAST) : 0;           // proposal2's α = 1 fast path (stage2.hpp A1F_*)
 #ifdef SMCMI_K3_CH2
@@ -1011,8 +996,8 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     if (!worker) {
         // ================================================================ GATHERER of local virtual shard vg
         const int vg = (int)blockIdx.x - W;
-        // (the gatherer stages a shard's rows - at most 2 GRP of them - in the dynamic LDS: launch2.hpp launch_k3_seg sizes it, k3_gather_lds_bytes)
-        double *g_stage = sm;                                    // (a gatherer uses none of the workers' dynamic LDS: model constants, proposal, parked draws)
+        // (the gatherer stages a shard's rows - at most 2 GRP of them - in the dynamic LDS: launch2.hpp launch_k3_seg sizes it)
+        double *g_stage = lds_at<double, O3[lds::S_gather]>(sm);    // (a gatherer uses none of the workers' dynamic LDS: model constants, proposal, parked draws)
         // (one hand-over per stage, see the workers: a stage whose correction rows ride the mutation rows in front of it has them swept and posted
         // BEFORE this block takes the mutation totals and runs the begin - the workers wait for the correction totals, nothing else)
         bool cm_posted = false;
@@ -1077,7 +1062,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     // ==================================================================== WORKER
     // the first proposal's random numbers of the NEXT stage, drawn while the block waits for that stage's begin (they depend on (seed,
     // particle, stage) only) and parked here, slot-major: z_park[slot * T3 + tid], slots = MH uniform, mixture uniform, D normals
-    double *z_park = sm + k3_park_offset(D);
+    double *z_park = lds_at<double, O3[lds::S_park]>(sm);
 #ifndef SMCMI_K3_CH2
     const int vl = (int)blockIdx.x % g.Vl, r = (int)blockIdx.x / g.Vl, rowi = vl * g.nb2 + r;       // row index = engine 2's block index
     const double pw = rp.pw, logp_old = rp.logp_old, nrm_N = ma.n_parts;
@@ -1125,7 +1110,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     int rowi = rowi_c[0];
     unsigned long long pid = (unsigned long long)(ma.gid0 + i);
     const unsigned long long pid_park = pid;                    // (the draws parked ahead are chunk 0's)
-    double *st2 = z_park + (D + 2) * T3;                        // CH = 2: the parked chunk [θ_1..θ_D | loglh | logprior | old_loglh | accept | W | W̃][T3]
+    double *st2 = lds_at<double, O3[lds::S_cols]>(sm);          // CH = 2: the parked chunk [θ_1..θ_D | loglh | logprior | old_loglh | accept | W | W̃][T3]
     double x[D], like, lprior, like_prev, Wt, acc_val;
     double v_entered;                                           // the unnormalised weight K1 left for the entered stage
     // (entered at the mutation of a stage that resampled: the gathered cloud is in buffer 1 - k2_gather - as K2 reads it)
@@ -1273,7 +1258,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             // would cost the stage loop 26 registers and 38 spills for a path one stage in twenty takes.  (A kernel whose static arrays leave no room
             // for the D + 5 columns - mixture proposals beyond n_para 7 - parks it in the block's slice of a scratch buffer in device memory instead:
             // the same thread writes and reads back every word, 60 KB per block that stay in the die's L2)
-            double *sto = z_park + (D + 2) * T3;
+            double *sto = lds_at<double, O3[lds::S_cols]>(sm);
             if constexpr (k3_sel_cols(D, ALPHA1) == 0) sto = sa.sel->transit + (long long)blockIdx.x * (D + 5) * T3;
             double *stx = sto + 5 * T3;
             __syncthreads();

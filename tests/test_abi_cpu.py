@@ -240,3 +240,50 @@ def test_stage_policy_states_the_rules_the_drivers_had(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.strip() == "ok" and r.stderr == "", r.stdout + r.stderr
+
+
+def _lds_check(tmp_path):
+    """tests/lds_check.cpp built with AddressSanitizer and UBSan and run: its standard output."""
+    import subprocess
+
+    exe = tmp_path / "lds_check"
+    r = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        os.path.join(ROOT, "tests", "lds_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().splitlines()[-1] == "ok" and r.stderr == "", r.stdout + r.stderr
+    return r.stdout
+
+
+def test_lds_layouts_state_the_sizes_the_launch_sites_had(tmp_path):
+    """tests/lds_check.cpp holds csrc/ldslayout.hpp - the one description of every stage kernel's dynamic LDS - against the size formulas the
+    launch sites stated by hand before (every total equal, at every n_para the layout is built for), checks every member's alignment, that no
+    two live members overlap and that all end inside the total, and the equivalences between the layouts; host code under AddressSanitizer
+    and UBSan, no HIP: exit status 0, "ok", nothing on stderr."""
+    _lds_check(tmp_path)
+
+
+def test_segment_kernels_fit_a_cu_with_the_static_lds_the_compiler_reports(tmp_path):
+    """Every k3_segment instantiation in the compiler's resource report: its static LDS plus the largest dynamic size launch_k3_seg asks for
+    (whole KB, as the kernel is opted in; printed by tests/lds_check.cpp from the layouts) fits a CU's 160 KB, and a mixture kernel's static
+    LDS is within what k3_sel_cols takes it to be when it decides whether the particle in transit stays in LDS: its z columns and dense
+    mixture block (counted by the rule itself) and 24 KB for all the rest."""
+    rep = os.path.join(ROOT, "smc.jl_amd", "csrc", "resource_usage.txt")
+    if not os.path.exists(rep):
+        pytest.skip("library was built without the resource report")
+    dyn = {}
+    for m in re.finditer(r"^k3_segment D=(\d+) alpha1=(\d) chunks=(\d) max_dynamic=(\d+) assumed_static=(\d+)$", _lds_check(tmp_path), re.M):
+        dyn[tuple(int(x) for x in m.group(1, 2, 3))] = (int(m.group(4)), int(m.group(5)))
+    assert len(dyn) == 30, sorted(dyn)
+    txt = open(rep).read()
+    seen = set()
+    for m in re.finditer(r"Function Name: _ZN5smcmi\d+k3_segmentILi(\d+)ELb([01])ELb([01])ELi(\d)ELb([01])E[^\n]*\n(?:[^\n]*\n){0,14}?[^\n]*LDS Size \[bytes/block\]: (\d+)", txt):
+        d, a1, ride, ch, sys_, static = (int(x) for x in m.groups())
+        max_dynamic, assumed_static = dyn[(d, a1, ch)]
+        print(f"k3_segment<{d}, {a1}, {ride}, {ch}, {sys_}>: static {static} + dynamic {max_dynamic} = {static + max_dynamic}")
+        assert static + max_dynamic <= 160 * 1024, (d, a1, ride, ch, sys_, static, max_dynamic)
+        if not a1:
+            assert static <= assumed_static, (d, a1, ride, ch, sys_, static, assumed_static)
+        seen.add((d, a1, ride, ch, sys_))
+    assert len(seen) == 100, len(seen)                        # 10 n_para x (4 one-handle + 4 several-handle + 2 two-chunk) instantiations
