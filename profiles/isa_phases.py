@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-phase static instruction census of the register mutation kernel (gfx950 ISA of `hipcc -S -DSMCMI_ISA_MARKS`): the kernel's phase
-stamps (SMCMI_PROF slots in csrc/kernels.hpp k_mutate_reg) become comments in the ISA and the instructions between two of them are
+stamps (MutRegPhase::at<slot> in csrc/kernels.hpp k_mutate_reg, mh_step and mh_draw) become comments in the ISA and the instructions between two of them are
 counted by class.  One MH proposal executes every phase between marks 3 and 8 once; the prologue (0-3) and epilogue (8-9) once per launch.
 usage: python profiles/isa_phases.py [out.json]      (no GPU needed)"""
 import collections

@@ -1824,7 +1824,7 @@ constexpr int PT = 1024;  // threads of the single prepare block
 // while block 0 of k_prepare_mutation does its serial set-up on one CU the rest of the chip is idle - blocks 1.. of the same
 // launch fill it with the Philox + Box-Muller work (~40 % of the mutation kernel's instructions), which the mutation kernel
 // then just loads.  Layout: zbuf[(t ZS + slot) n + i], t = mh_step n_blocks + block, ZS = D + 2 slots: MH uniform, mixture
-// uniform, D normals (zero beyond the block length).  Same tags and the same expressions as the in-kernel path -> same bits.
+// uniform, D normals (zero beyond the block length).  Same tags and the same expressions as the in-kernel path (mh_draw) -> same bits.
 constexpr int RA_T = 256;
 constexpr int RA_SKIP = 16;     // blocks 1..15 of k_prepare_mutation draw nothing (block 0 prepares, the others may total rows): see rng_ahead_block
 
@@ -1856,6 +1856,8 @@ __device__ inline void rng_ahead_block(const DevState *st, const ModelDev *md, u
             const int b = tt % nb;
             const int db = (b < nb - 1) ? sub : nf - sub * (nb - 1);
             double step_prob, u_dummy, uc, unext;
+            // (these three lines must mirror mh_draw's first three, tag for tag and word for word: the mutation kernels take a proposal's
+            // numbers from here or from mh_draw and must see the same bits - tests/test_gpu_fixed_select.py, tests/test_gpu_mutation_bits.py)
             if (t == 0) uniform_pair(seed, pid, stage, rng_tag(P_MUT, 0xFFFFFu, 0), step_prob, u_dummy);
             else uniform_pair(seed, pid, stage, rng_tag(P_MUT, t - 1, 0), u_dummy, step_prob);
             uniform_pair(seed, pid, stage, rng_tag(P_MUT, t, 0), uc, unext);
@@ -2629,6 +2631,161 @@ SMCMI_FP_CONTRACT
     return log(q0 / q1);
 }
 
+// ---- the MH move of one particle in the register kernels (n_para <= 10), written once: engine 1's k_mutate_reg below and engine 2 / 3's
+// k2_mh_steps (stage2.hpp: k2_mutate, k2b_mutate, k3_segment) keep their own step x block loops - barriers, where the factor is expanded,
+// where the log-determinant and the mixture matrices come from, which draws are loaded - and call these for everything inside them.
+// A phase hook: at<SLOT>() where a kernel stamps its phases (k_mutate_reg: MutRegPhase), mark<SLOT>() where only the ISA census
+// (-DSMCMI_ISA_MARKS) has a boundary.  The default does nothing, and leaves no scheduling barrier behind.
+struct NoPhase {
+    template <int SLOT> __device__ __forceinline__ void at() const {}
+    template <int SLOT> __device__ __forceinline__ void mark() const {}
+};
+// Random numbers of proposal t (mh_step * n_blocks + block) of one particle (src/mutation.jl:66,133, helpers.jl:87-100; RNG
+// contract in DESIGN.md): the MH uniform of this decision, the mixture-component uniform and the block's normals.  Box-Muller is
+// written stage by stage over the pairs so the independent log / sqrt / sincospi chains can be interleaved by the scheduler (at <= 2
+// wavefronts per SIMD dependent FP64 latency is exposed).
+template <int D, class PH = NoPhase>
+__device__ inline void mh_draw(unsigned long long seed, unsigned long long pid, unsigned stage, unsigned t, int db, double &step_prob, double &uc,
+                               double (&z)[D], const PH &ph = PH{}) {
+SMCMI_FP_CONTRACT
+    double u_dummy, unext;
+    if (t == 0) uniform_pair(seed, pid, stage, rng_tag(P_MUT, 0xFFFFFu, 0), step_prob, u_dummy);       // quirk Q3: drawn before the proposal
+    else uniform_pair(seed, pid, stage, rng_tag(P_MUT, t - 1, 0), u_dummy, step_prob);
+    uniform_pair(seed, pid, stage, rng_tag(P_MUT, t, 0), uc, unext);
+    constexpr int NP2 = (D + 1) / 2;
+    constexpr int GRP = 3;                     // pairs interleaved at a time (more raises register pressure past 2 waves/SIMD)
+    double ua[NP2], ub[NP2], rr[NP2], sn[NP2], cs[NP2];
+#pragma unroll
+    for (int q = 0; q < NP2; ++q) {
+        ua[q] = 0.5; ub[q] = 0.0;
+        if (2 * q < db) uniform_pair(seed, pid, stage, rng_tag(P_MUT, t, 1 + q), ua[q], ub[q]);
+    }
+    ph.template mark<31>();
+#pragma unroll
+    for (int g0 = 0; g0 < NP2; g0 += GRP) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = g0; q < g0 + GRP && q < NP2; ++q) rr[q] = bx_neg2log(ua[q]);
+#pragma unroll
+        for (int q = g0; q < g0 + GRP && q < NP2; ++q) rr[q] = bx_sqrt(rr[q]);
+#pragma unroll
+        for (int q = g0; q < g0 + GRP && q < NP2; ++q) bx_sincos2pi(ub[q], &sn[q], &cs[q]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NP2; ++q) {
+        z[2 * q] = (2 * q < db) ? rr[q] * cs[q] : 0.0;
+        if (2 * q + 1 < D) z[2 * q + 1] = (2 * q + 1 < db) ? rr[q] * sn[q] : 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < D; ++e) asm volatile("" : "+v"(z[e]));   // materialise the normals here (see the matvec note)
+}
+// The two likelihood descriptors as views for the mutation body; data that fits is staged in LDS (l_dat, LIK_LDS_CAP doubles) by the
+// whole block of T threads - the caller's next barrier publishes it.
+__device__ inline void stage_lik(const LikDev &ld0, const LikDev &ld1, double *l_par, double *l_dat, int T, LikView (&lv)[2]) {
+    const int tid = threadIdx.x;
+    int used = 0;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const LikDev &ld = q == 0 ? ld0 : ld1;
+        const long long nd = ld.rows * ld.cols, na = ld.aux_rows * ld.aux_cols;
+        const bool fits = ld.family >= 0 && ld.family != SMCMI_LIK_CAPM_LITERAL && used + nd + na <= LIK_LDS_CAP;   // (capm_literal reads its data as scalars)
+        if (fits) {
+            for (long long k = tid; k < nd; k += T) l_dat[used + k] = ld.data[k];
+            for (long long k = tid; k < na; k += T) l_dat[used + nd + k] = ld.aux[k];
+        }
+        lv[q] = LikView{ld.family, l_par + q * LIK_PAR_MAX, ld.c0, fits ? l_dat + used : ld.data, ld.rows, ld.cols,
+                        fits ? l_dat + used + nd : ld.aux, ld.aux_rows, ld.aux_cols};
+        if (fits) used += (int)(nd + na);
+    }
+}
+// α = 1 only ever draws θ_b + L z.  Store the block's factor L (packed d_b x d_b, lower triangle) with its rows scattered to NATURAL
+// parameter order, M[k][:] = L[e][:] for k = ball[e] (zero rows elsewhere): the proposal becomes x_k + Σ_e M[k][e] z_e with compile-time
+// indices - no gather / scatter of the parameter vector at all (the added zero terms do not change any sum).  All T threads of the block
+// call; the callers keep their own barriers around it.
+template <int D>
+__device__ inline void expand_alpha1_factor(double *Ls, const double *L, const int *ball, int db, int T, int tid) {
+    for (int e = tid; e < D * D; e += T) Ls[e] = 0.0;
+    __syncthreads();
+    for (int e = tid; e < db * db; e += T) {
+        const int r = e / db, cidx = e % db;
+        if (cidx <= r) Ls[cidx * D + ball[r]] = L[r * db + cidx];   // transposed: Ls[e][k] = M[k][e]
+    }
+}
+// The target at the proposal x: log-prior, log-likelihood on the new data (-Inf there takes the prior with it) and on the old data; the
+// three stay -Inf outside the bounds.  debug & 2: a stub that needs no model (parity tests of the draws).
+template <int D>
+__device__ __forceinline__ void eval_target(const ModelView &mv, const LikView (&lv)[2], int has_other, int debug, const double (&x)[D], double zz2,
+                                            double like, double lprior, double &prior_new, double &like_new, double &like_old_data) {
+SMCMI_FP_CONTRACT
+    auto XN = [&](int k) { return x[k]; };
+    if (debug & 2) { prior_new = lprior - 0.1 * zz2; like_new = like - 0.2; like_old_data = 0.0; }
+    else if (in_bounds_s<D>(mv, XN)) {
+        prior_new = logprior_s<D>(mv, XN, has_other);
+        like_new = loglik_s<D>(lv[0], XN);
+        if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
+        like_old_data = (lv[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik_s<D>(lv[1], XN);
+    }
+}
+// One proposal of one particle (src/mutation.jl:86-138; helpers.jl:87-164 for α < 1): from the block's normals z, the mixture uniform uc
+// and the MH uniform step_prob to the updated (x, like, lprior, like_prev, accept).  Ls: the block's factor as expand_alpha1_factor leaves
+// it and logdet_b its log-determinant (α = 1); M: the block's dense mixture matrices (α < 1; MixDense in LDS or MixDenseC through the
+// constant address space); zt: this thread's private LDS column, stride T (α < 1).
+template <int D, bool ALPHA1, int T, class MX, class PH = NoPhase>
+__device__ __forceinline__ void mh_step(const double *Ls, double logdet_b, int db, const MX &M, const LikView (&lv)[2], const ModelView &mv, int has_other,
+                                        int debug, double c_alpha, double phi_n, double *zt, const double (&z)[D], double uc, double step_prob,
+                                        double (&x)[D], double &like, double &lprior, double &like_prev, double &accept, const PH &ph = PH{}) {
+SMCMI_FP_CONTRACT
+    double prior_new = SMCMI_NEG_INF, like_new = SMCMI_NEG_INF, like_old_data = SMCMI_NEG_INF;
+    double q0 = 0.0, q1 = 0.0;
+    double xo[D];
+    double zz2 = 0.0;
+#pragma unroll
+    for (int e = 0; e < D; ++e) zz2 += z[e] * z[e];
+    if constexpr (ALPHA1) {
+        // q0 = q1 = log N(θ_b; ϑ_b, c²Σ) bit for bit (sign-symmetric quadratic form), other mixture terms have weight 0:
+        // q0 - q1 == 0 unless exp() underflows to 0 (log-density < -745.13: the reference gets NaN and rejects).
+        q1 = (-((double)db * LOG2PI + logdet_b + zz2) / 2.0 < -745.1332191019412) ? __builtin_nan("") : 0.0;
+        ph.template at<5>();
+        // column sweep: D independent accumulators (one per parameter), one factor column live at a time; every
+        // accumulator still adds its terms in ascending e, i.e. the same order as the row-wise triangular product
+        double sacc[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) { xo[k] = x[k]; sacc[k] = 0.0; }
+#pragma unroll
+        for (int e = 0; e < D; ++e) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) sacc[k] += Ls[e * D + k] * z[e];
+            // pin the accumulators here: otherwise the optimiser sinks all FMAs to the use site and keeps the whole
+            // factor (100 LDS values = 200 VGPRs) live, which costs the second wavefront per SIMD
+#pragma unroll
+            for (int k = 0; k < D; ++k) asm volatile("" : "+v"(sacc[k]));
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = xo[k] + sacc[k];
+        ph.template at<6>();
+    } else {
+        // mixture draw + proposal densities in parameter order (mix_propose above): no gather / scatter, no division
+        ph.template at<5>();
+        double xn[D];
+        q0 = mix_propose<D, T>(M, x, z, uc, c_alpha, (debug & 4) != 0, zt, xn);       // q0 - q1 as one number
+        ph.template at<6>();
+#pragma unroll
+        for (int k = 0; k < D; ++k) { xo[k] = x[k]; x[k] = xn[k]; }
+    }
+    eval_target<D>(mv, lv, has_other, debug, x, zz2, like, lprior, prior_new, like_new, like_old_data);
+    ph.template at<7>();
+    const double eta = exp(phi_n * (like_new - like) + (1.0 - phi_n) * (like_old_data - like_prev) +
+                           (prior_new - lprior) + (q0 - q1));
+    if (step_prob < eta) {
+        like = like_new; lprior = prior_new; like_prev = like_old_data;
+        accept += (double)db;
+    } else {
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = xo[k];
+    }
+}
+
 // The dense mixture matrices of every block of the stage, once per stage by one block (the register kernel's blocks hold 256
 // particles each: inverting and expanding per block costs more than the mutation itself once the cloud is large).
 template <int D>
@@ -2701,6 +2858,49 @@ __global__ void __launch_bounds__(256) k_debug_mix_densities(const double *para_
     }
 }
 
+// The mutation body's LDS arrays (ldslayout.hpp lds::mut2, its M_BODY_N members): what k_mutate_reg carves, and the front of engine 2's
+// Mut2Lds (stage2.hpp).  red_n, lik_cap: as the layout's.
+template <int D>
+struct MutBodyLds {
+    double *Ls, *red, *m_lo, *m_hi, *m_a, *m_b, *m_k, *l_par, *l_dat, *Lraw, *logdet_s, *mub_raw, *sdd_raw, *sdn_raw;
+    int *m_fix, *m_fam, *bptr_s, *loff_s, *ball_raw;
+    template <int RED_N, int CAP>
+    __device__ void place_body(double *sm) {
+        using namespace lds;
+        constexpr Mut2Layout O = mut2(D, RED_N, CAP, false);
+        Ls = lds_at<double, O[M_Ls]>(sm); red = lds_at<double, O[M_red]>(sm);
+        m_lo = lds_at<double, O[M_lo]>(sm); m_hi = lds_at<double, O[M_hi]>(sm); m_a = lds_at<double, O[M_a]>(sm); m_b = lds_at<double, O[M_b]>(sm);
+        m_k = lds_at<double, O[M_k]>(sm); l_par = lds_at<double, O[M_lpar]>(sm); l_dat = lds_at<double, O[M_ldat]>(sm); Lraw = lds_at<double, O[M_Lraw]>(sm);
+        logdet_s = lds_at<double, O[M_logdet]>(sm); mub_raw = lds_at<double, O[M_mub]>(sm); sdd_raw = lds_at<double, O[M_sddr]>(sm);
+        sdn_raw = lds_at<double, O[M_sdnr]>(sm);
+        m_fix = lds_at<int, O[M_fix]>(sm); m_fam = lds_at<int, O[M_fam]>(sm); bptr_s = lds_at<int, O[M_bptr]>(sm);
+        loff_s = lds_at<int, O[M_loff]>(sm); ball_raw = lds_at<int, O[M_ballr]>(sm);
+    }
+};
+// k_mutate_reg's phase stamps (mh_step's hook): a scheduling barrier in every build - the kernel's register allocation is tuned with
+// them -, the phase boundary as a comment in the ISA under -DSMCMI_ISA_MARKS (profiles/isa_phases.py: the per-phase instruction census),
+// and the shader clock into the profile buffer for the two blocks a profiled launch watches.
+#ifdef SMCMI_ISA_MARKS
+#define SMCMI_MARK(slot) asm volatile("; SMCMI_MARK %0" ::"n"(slot) : "memory")
+#else
+#define SMCMI_MARK(slot) (void)0
+#endif
+struct MutRegPhase {
+    bool me;
+    long long *p;
+    template <int SLOT> __device__ __forceinline__ void at() const {
+        __builtin_amdgcn_sched_barrier(0);
+        SMCMI_MARK(SLOT);
+        if (me) { unsigned long long tt_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt_)::"memory"); p[SLOT] = (long long)tt_; }
+    }
+    template <int SLOT> __device__ __forceinline__ void mark() const {
+#ifdef SMCMI_ISA_MARKS
+        __builtin_amdgcn_sched_barrier(0);
+        SMCMI_MARK(SLOT);
+#endif
+    }
+};
+#undef SMCMI_MARK
 // Register-resident mutation for models with D = n_para <= 10 (MODE 0 of k_mutate, same arithmetic in the same order).
 // Everything per-particle lives in VGPRs with compile-time indices: the parameter vector x[D], and the block's z / draw /
 // solve vectors (padded to D entries; identity-padded factor).  Block membership is a run-time (but wave-uniform) index,
@@ -2713,29 +2913,10 @@ __global__ void __launch_bounds__(256, 3) k_mutate_reg(CloudPtrs cl, const DevSt
 SMCMI_FP_CONTRACT
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int T = blockDim.x, tid = threadIdx.x;
-    const bool profme = ma.prof != nullptr && tid == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2);
-    long long *profp = ma.prof + (blockIdx.x == 0 ? 0 : 16);
-    // (-DSMCMI_ISA_MARKS, profiles/isa_phases.py: the phase boundaries as comments in the ISA - the per-phase instruction census)
-#ifdef SMCMI_ISA_MARKS
-#define SMCMI_MARK(slot) asm volatile("; SMCMI_MARK " #slot ::: "memory")
-#else
-#define SMCMI_MARK(slot) (void)0
-#endif
-#define SMCMI_PROF(slot)                                                                                    \
-    do {                                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-        SMCMI_MARK(slot);                                                                                   \
-        if (profme) { unsigned long long tt_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt_)::"memory"); profp[slot] = (long long)tt_; } \
-    } while (0)
-    SMCMI_PROF(0);
-    using namespace lds;
-    constexpr Mut2Layout O = mut2(D, 4, LIK_LDS_CAP, false);        // (the mutation body's arrays as in Mut2Lds; four wavefronts: red[4])
-    double *Ls = lds_at<double, O[M_Ls]>(sm), *red = lds_at<double, O[M_red]>(sm), *m_lo = lds_at<double, O[M_lo]>(sm), *m_hi = lds_at<double, O[M_hi]>(sm);
-    double *m_a = lds_at<double, O[M_a]>(sm), *m_b = lds_at<double, O[M_b]>(sm), *m_k = lds_at<double, O[M_k]>(sm), *l_par = lds_at<double, O[M_lpar]>(sm);
-    double *l_dat = lds_at<double, O[M_ldat]>(sm), *Lraw = lds_at<double, O[M_Lraw]>(sm), *logdet_s = lds_at<double, O[M_logdet]>(sm);
-    double *mub_raw = lds_at<double, O[M_mub]>(sm), *sdd_raw = lds_at<double, O[M_sddr]>(sm), *sdn_raw = lds_at<double, O[M_sdnr]>(sm);
-    int *m_fix = lds_at<int, O[M_fix]>(sm), *m_fam = lds_at<int, O[M_fam]>(sm), *bptr_s = lds_at<int, O[M_bptr]>(sm), *loff_s = lds_at<int, O[M_loff]>(sm);
-    int *ball_raw = lds_at<int, O[M_ballr]>(sm);
+    const MutRegPhase ph{ma.prof != nullptr && tid == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2), ma.prof + (blockIdx.x == 0 ? 0 : 16)};
+    ph.at<0>();
+    MutBodyLds<D> B;
+    B.template place_body<4, LIK_LDS_CAP>(sm);        // (four wavefronts: red[4])
     // ---- round 1: every uniform input of the launch, issued back to back (a dependent global round trip costs ~1 µs
     // at this occupancy, so the kernel is organised as: one round of parameter loads, one round of particle loads,
     // compute, one round of stores).  nb / nf are launch arguments so the copy extents do not depend on loaded data.
@@ -2746,21 +2927,21 @@ SMCMI_FP_CONTRACT
     const bool es_uniform = st->do_resample != 0;       // this stage resampled: all weights are 1
     const double nrm_N = (double)st->rp.n_parts, nrm_sumw = st->sumw;       // only used with ma.normalize
     const int nrm_col = st->stage - 1, nrm_hist = st->rp.store_history;
-    for (int e = tid; e < nf * nf; e += T) Lraw[e] = st->L[e];
+    for (int e = tid; e < nf * nf; e += T) B.Lraw[e] = st->L[e];
     for (int e = tid; e < nf; e += T) {
-        mub_raw[e] = st->mu_b[e]; sdd_raw[e] = st->sd_draw[e]; sdn_raw[e] = st->sd_dens[e]; ball_raw[e] = st->blocks_all[e];
+        B.mub_raw[e] = st->mu_b[e]; B.sdd_raw[e] = st->sd_draw[e]; B.sdn_raw[e] = st->sd_dens[e]; B.ball_raw[e] = st->blocks_all[e];
     }
-    for (int b = tid; b < nb; b += T) { loff_s[b] = st->l_off[b]; logdet_s[b] = st->logdet[b]; }
-    for (int b = tid; b <= nb; b += T) bptr_s[b] = st->block_ptr[b];
+    for (int b = tid; b < nb; b += T) { B.loff_s[b] = st->l_off[b]; B.logdet_s[b] = st->logdet[b]; }
+    for (int b = tid; b <= nb; b += T) B.bptr_s[b] = st->block_ptr[b];
     for (int k = tid; k < D; k += T) {
-        m_lo[k] = md->lo[k]; m_hi[k] = md->hi[k]; m_a[k] = md->prior_a[k]; m_b[k] = md->prior_b[k]; m_k[k] = md->prior_k[k];
-        m_fix[k] = md->fixed[k]; m_fam[k] = md->prior_family[k];
+        B.m_lo[k] = md->lo[k]; B.m_hi[k] = md->hi[k]; B.m_a[k] = md->prior_a[k]; B.m_b[k] = md->prior_b[k]; B.m_k[k] = md->prior_k[k];
+        B.m_fix[k] = md->fixed[k]; B.m_fam[k] = md->prior_family[k];
     }
-    for (int k = tid; k < 2 * LIK_PAR_MAX; k += T) l_par[k] = md->lik[k / LIK_PAR_MAX].par[k % LIK_PAR_MAX];
+    for (int k = tid; k < 2 * LIK_PAR_MAX; k += T) B.l_par[k] = md->lik[k / LIK_PAR_MAX].par[k % LIK_PAR_MAX];
     const LikDev ld0 = md->lik[0], ld1 = md->lik[1];
     const int has_other = md->has_other_priors;
     if (!standalone && done) return;
-    SMCMI_PROF(1);
+    ph.at<1>();
     // ---- round 2: the particle and the likelihood data
     const long long i = (long long)blockIdx.x * T + tid;
     const bool live = i < cl.n;
@@ -2783,52 +2964,23 @@ SMCMI_FP_CONTRACT
             if (ma.hist_W && nrm_hist) ma.hist_W[(long long)nrm_col * ma.hist_ld + i] = w_part;
         }
     }
-    ModelView mv{D, m_fix, m_fam, m_lo, m_hi, m_a, m_b, m_k};
+    ModelView mv{D, B.m_fix, B.m_fam, B.m_lo, B.m_hi, B.m_a, B.m_b, B.m_k};
     LikView lv[2];
-    {
-        int used = 0;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const LikDev &ld = q == 0 ? ld0 : ld1;
-            const long long nd = ld.rows * ld.cols, na = ld.aux_rows * ld.aux_cols;
-            const bool fits = ld.family >= 0 && ld.family != SMCMI_LIK_CAPM_LITERAL && used + nd + na <= LIK_LDS_CAP;   // (capm_literal reads its data as scalars)
-            if (fits) {
-                for (long long k = tid; k < nd; k += T) l_dat[used + k] = ld.data[k];
-                for (long long k = tid; k < na; k += T) l_dat[used + nd + k] = ld.aux[k];
-            }
-            lv[q] = LikView{ld.family, l_par + q * LIK_PAR_MAX, ld.c0, fits ? l_dat + used : ld.data, ld.rows, ld.cols,
-                            fits ? l_dat + used + nd : ld.aux, ld.aux_rows, ld.aux_cols};
-            if (fits) used += (int)(nd + na);
-        }
-    }
-    SMCMI_PROF(2);
-    auto XN = [&](int k) { return x[k]; };
+    stage_lik(ld0, ld1, B.l_par, B.l_dat, T, lv);
+    ph.at<2>();
     __shared__ double mixzt[ALPHA1 ? 1 : 256 * D];             // private z columns of the diagonal component's draw
     for (int step = 0; step < n_steps; ++step) {
         for (int b = 0; b < nb; ++b) {
             if (nb > 1 || step == 0) __syncthreads();   // raw copies (first pass) / previous block's readers (later passes)
-            const int p0 = bptr_s[b], db = bptr_s[b + 1] - p0;
+            const int p0 = B.bptr_s[b], db = B.bptr_s[b + 1] - p0;
             if (nb > 1 || step == 0) {              // expand this block's constants to the padded D x D form
-                const double *L = Lraw + loff_s[b];
-                if constexpr (ALPHA1) {
-                    // α = 1 only ever draws θ_b + L z.  Store the factor with its rows scattered to NATURAL parameter
-                    // order, M[k][:] = L[e][:] for k = blocks_all[e] (zero rows elsewhere): the proposal becomes
-                    // x_k + Σ_e M[k][e] z_e with compile-time indices - no gather / scatter of the parameter vector at all
-                    // (the added zero terms do not change any sum).
-                    for (int e = tid; e < D * D; e += T) Ls[e] = 0.0;
-                    __syncthreads();
-                    for (int e = tid; e < db * db; e += T) {
-                        const int r = e / db, cidx = e % db;
-                        if (cidx <= r) Ls[cidx * D + ball_raw[p0 + r]] = L[r * db + cidx];   // transposed: Ls[e][k] = M[k][e]
-                    }
-                }
+                if constexpr (ALPHA1) expand_alpha1_factor<D>(B.Ls, B.Lraw + B.loff_s[b], B.ball_raw + p0, db, T, tid);
                 __syncthreads();
             }
-            SMCMI_PROF(3);
+            ph.at<3>();
             if (!live) continue;
             const unsigned t = (unsigned)(step * nb + b);
-            double step_prob, u_dummy;     // MH uniform for this decision: drawn "before" the proposal (quirk Q3)
-            double uc, unext;
+            double step_prob, uc;          // the MH uniform of this decision, the mixture-component uniform
             double z[D];
 #ifdef SMCMI_COUNT_RNG_AHEAD   // profiles/isa_count.py: instruction mix of the path that loads the draws (dead-codes the in-kernel RNG)
             constexpr bool z_only = true;
@@ -2842,116 +2994,19 @@ SMCMI_FP_CONTRACT
                 uc = zt[cl.n];
 #pragma unroll
                 for (int e = 0; e < D; ++e) z[e] = zt[(long long)(2 + e) * cl.n];
-            } else {
-            if (t == 0) uniform_pair(ma.seed, pid, stage, rng_tag(P_MUT, 0xFFFFFu, 0), step_prob, u_dummy);
-            else uniform_pair(ma.seed, pid, stage, rng_tag(P_MUT, t - 1, 0), u_dummy, step_prob);
-            // ---- mvnormal_mixture_draw (src/helpers.jl:87-100)
-            uniform_pair(ma.seed, pid, stage, rng_tag(P_MUT, t, 0), uc, unext);
-            {
-                // Box-Muller for the block, written stage by stage over all pairs so the independent log / sqrt / sincospi
-                // chains can be interleaved by the scheduler (at <= 2 wavefronts per SIMD dependent FP64 latency is exposed)
-                constexpr int NP2 = (D + 1) / 2;
-                constexpr int GRP = 3;                     // pairs interleaved at a time (more raises register pressure past 2 waves/SIMD)
-                double ua[NP2], ub[NP2], rr[NP2], sn[NP2], cs[NP2];
-#pragma unroll
-                for (int q = 0; q < NP2; ++q) {
-                    ua[q] = 0.5; ub[q] = 0.0;
-                    if (2 * q < db) uniform_pair(ma.seed, pid, stage, rng_tag(P_MUT, t, 1 + q), ua[q], ub[q]);
-                }
-#ifdef SMCMI_ISA_MARKS
-                __builtin_amdgcn_sched_barrier(0);
-                SMCMI_MARK(31);
-#endif
-#pragma unroll
-                for (int g0 = 0; g0 < NP2; g0 += GRP) {
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int q = g0; q < g0 + GRP && q < NP2; ++q) rr[q] = bx_neg2log(ua[q]);
-#pragma unroll
-                    for (int q = g0; q < g0 + GRP && q < NP2; ++q) rr[q] = bx_sqrt(rr[q]);
-#pragma unroll
-                    for (int q = g0; q < g0 + GRP && q < NP2; ++q) bx_sincos2pi(ub[q], &sn[q], &cs[q]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < NP2; ++q) {
-                    z[2 * q] = (2 * q < db) ? rr[q] * cs[q] : 0.0;
-                    if (2 * q + 1 < D) z[2 * q + 1] = (2 * q + 1 < db) ? rr[q] * sn[q] : 0.0;
-                }
-#pragma unroll
-                for (int e = 0; e < D; ++e) asm volatile("" : "+v"(z[e]));   // materialise the normals here (see the matvec note)
-            }
-            }
-            SMCMI_PROF(4);
-            double prior_new = SMCMI_NEG_INF, like_new = SMCMI_NEG_INF, like_old_data = SMCMI_NEG_INF;
-            double q0 = 0.0, q1 = 0.0;
-            double xo[D];
-            if constexpr (ALPHA1) {
-                double zz2 = 0.0;
-#pragma unroll
-                for (int e = 0; e < D; ++e) zz2 += z[e] * z[e];
-                // q0 = q1 = log N(θ_b; ϑ_b, c²Σ) bit for bit (sign-symmetric quadratic form), other mixture terms have weight 0:
-                // q0 - q1 == 0 unless exp() underflows to 0 (log-density < -745.13: the reference gets NaN and rejects).
-                q1 = (-((double)db * LOG2PI + logdet_s[b] + zz2) / 2.0 < -745.1332191019412) ? __builtin_nan("") : 0.0;
-                SMCMI_PROF(5);
-                // column sweep: D independent accumulators (one per parameter), one factor column live at a time; every
-                // accumulator still adds its terms in ascending e, i.e. the same order as the row-wise triangular product
-                double sacc[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) { xo[k] = x[k]; sacc[k] = 0.0; }
-#pragma unroll
-                for (int e = 0; e < D; ++e) {
-#pragma unroll
-                    for (int k = 0; k < D; ++k) sacc[k] += Ls[e * D + k] * z[e];
-                    // pin the accumulators here: otherwise the optimiser sinks all FMAs to the use site and keeps the whole
-                    // factor (100 LDS values = 200 VGPRs) live, which costs the second wavefront per SIMD
-#pragma unroll
-                    for (int k = 0; k < D; ++k) asm volatile("" : "+v"(sacc[k]));
-                }
-#pragma unroll
-                for (int k = 0; k < D; ++k) x[k] = xo[k] + sacc[k];
-                SMCMI_PROF(6);
-                if (ma.debug & 2) { prior_new = lprior - 0.1 * zz2; like_new = like - 0.2; like_old_data = 0.0; }
-                else if (in_bounds_s<D>(mv, XN)) {
-                    prior_new = logprior_s<D>(mv, XN, has_other);
-                    like_new = loglik_s<D>(lv[0], XN);
-                    if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
-                    like_old_data = (lv[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik_s<D>(lv[1], XN);
-                }
-            } else {
-            // mixture draw + proposal densities in parameter order (mix_propose above): no gather / scatter, no division
-            double zz2 = 0.0;
-#pragma unroll
-            for (int e = 0; e < D; ++e) zz2 += z[e] * z[e];
-            SMCMI_PROF(5);
-            double xn[D];
-            // (this block's dense matrices, written by k_mix_prepare, read as wave-uniform scalars)
-            const MixDenseC<D> MX((mix_cdp)(unsigned long long)(ma.mix + (long long)b * MixDenseC<D>::DOUBLES), (mix_cip)(unsigned long long)(ma.mixpos + b * D));
-            q0 = mix_propose<D, 256>(MX, x, z, uc, c_alpha, (ma.debug & 4) != 0, mixzt + tid, xn);       // q0 - q1 as one number
-            SMCMI_PROF(6);
-#pragma unroll
-            for (int k = 0; k < D; ++k) { xo[k] = x[k]; x[k] = xn[k]; }
-            if (ma.debug & 2) { prior_new = lprior - 0.1 * zz2; like_new = like - 0.2; like_old_data = 0.0; }
-            else if (in_bounds_s<D>(mv, XN)) {
-                prior_new = logprior_s<D>(mv, XN, has_other);
-                like_new = loglik_s<D>(lv[0], XN);
-                if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
-                like_old_data = (lv[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik_s<D>(lv[1], XN);
-            }
-            }
-            SMCMI_PROF(7);
-            const double eta = exp(phi_n * (like_new - like) + (1.0 - phi_n) * (like_old_data - like_prev) +
-                                   (prior_new - lprior) + (q0 - q1));
-            if (step_prob < eta) {
-                like = like_new; lprior = prior_new; like_prev = like_old_data;
-                accept += (double)db;
-            } else {
-#pragma unroll
-                for (int k = 0; k < D; ++k) x[k] = xo[k];
-            }
+            } else
+                mh_draw<D>(ma.seed, pid, stage, t, db, step_prob, uc, z, ph);
+            ph.at<4>();
+            auto propose = [&](const auto &MX) __attribute__((always_inline)) {
+                mh_step<D, ALPHA1, 256>(B.Ls, B.logdet_s[b], db, MX, lv, mv, has_other, ma.debug, c_alpha, phi_n, mixzt + tid, z, uc, step_prob, x, like, lprior,
+                                        like_prev, accept, ph);
+            };
+            // α < 1: this block's dense matrices, written by k_mix_prepare, read as wave-uniform scalars; α = 1 has none (ma.mix may be null)
+            if constexpr (ALPHA1) propose(nullptr);
+            else propose(MixDenseC<D>((mix_cdp)(unsigned long long)(ma.mix + (long long)b * MixDenseC<D>::DOUBLES), (mix_cip)(unsigned long long)(ma.mixpos + b * D)));
         }
     }
-    SMCMI_PROF(8);
+    ph.at<8>();
     double acc_val = 0.0;
     if (live) {
 #pragma unroll
@@ -2970,26 +3025,23 @@ SMCMI_FP_CONTRACT
     double em = energy_or_ninf(like, energy_base(like_prev, st->rp.pw, st->rp.logp_old), (ma.esum && !es_uniform) ? w_part : 1.0, live);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) em = fmax(em, __shfl_xor(em, off, 64));
-    if ((tid & 63) == 0) { red[tid >> 6] = a1[0]; emx[tid >> 6] = em; }
+    if ((tid & 63) == 0) { B.red[tid >> 6] = a1[0]; emx[tid >> 6] = em; }
     if (ma.esum) {                                   // energy power sums of the mutated cloud (ϕ predictor of the next stage)
         double es[ES];
         energy_terms(es, w_part, like, like_prev, e_center, live, es_uniform);
         es[EACC] = acc_val;
-        const double tot = block_reduce_es(es, l_dat, T / 64);       // likelihood data in LDS is dead by now
+        const double tot = block_reduce_es(es, B.l_dat, T / 64);       // likelihood data in LDS is dead by now
         if (tid < ES) ma.esum[(long long)blockIdx.x * ES + tid] = tot;
     }
     __syncthreads();
     if (tid == 0) {
         double s = 0.0, m = emx[0];
-        for (int w = 0; w < T / 64; ++w) s += red[w];
+        for (int w = 0; w < T / 64; ++w) s += B.red[w];
         for (int w = 1; w < T / 64; ++w) m = fmax(m, emx[w]);
         acc_partials[blockIdx.x] = s;
         if (ma.emax) ma.emax[blockIdx.x] = m;
     }
-    SMCMI_PROF(9);
-#undef SMCMI_PROF
-#undef SMCMI_MARK
-#undef SMCMI_MARK
+    ph.at<9>();
 }
 
 // ------------------------------------------------------------------------------------------------ initial draw

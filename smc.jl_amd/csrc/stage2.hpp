@@ -812,51 +812,12 @@ static __global__ void __launch_bounds__(T1) k2_finish(DevState *st, Ctl2 *ctl, 
 }
 #endif
 
-// Random numbers of proposal t (mh_step * n_blocks + block) of one particle (src/mutation.jl:66,133, helpers.jl:87-100; RNG
-// contract in DESIGN.md): the MH uniform of this decision, the mixture-component uniform and the block's normals.  Box-Muller is
-// written stage by stage over the pairs so the independent log / sqrt / sincospi chains interleave.
-template <int D>
-__device__ inline void draw2(unsigned long long seed, unsigned long long pid, unsigned stage, unsigned t, int db, int debug, double &step_prob,
-                             double &uc, double (&z)[D]) {
-SMCMI_FP_CONTRACT
-    double u_dummy, unext;
-    if (t == 0) uniform_pair(seed, pid, stage, rng_tag(P_MUT, 0xFFFFFu, 0), step_prob, u_dummy);       // quirk Q3: drawn before the proposal
-    else uniform_pair(seed, pid, stage, rng_tag(P_MUT, t - 1, 0), u_dummy, step_prob);
-    uniform_pair(seed, pid, stage, rng_tag(P_MUT, t, 0), uc, unext);
-    constexpr int NP2 = (D + 1) / 2;
-    constexpr int GRPB = 3;                     // pairs interleaved at a time (more raises register pressure)
-    double ua[NP2], ub[NP2], rr[NP2], sn[NP2], cs[NP2];
-#pragma unroll
-    for (int q = 0; q < NP2; ++q) {
-        ua[q] = 0.5; ub[q] = 0.0;
-        if (2 * q < db) uniform_pair(seed, pid, stage, rng_tag(P_MUT, t, 1 + q), ua[q], ub[q]);
-    }
-#pragma unroll
-    for (int g0 = 0; g0 < NP2; g0 += GRPB) {
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = g0; q < g0 + GRPB && q < NP2; ++q) rr[q] = bx_neg2log(ua[q]);
-#pragma unroll
-        for (int q = g0; q < g0 + GRPB && q < NP2; ++q) rr[q] = bx_sqrt(rr[q]);
-#pragma unroll
-        for (int q = g0; q < g0 + GRPB && q < NP2; ++q) bx_sincos2pi(ub[q], &sn[q], &cs[q]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < NP2; ++q) {
-        z[2 * q] = (2 * q < db) ? rr[q] * cs[q] : 0.0;
-        if (2 * q + 1 < D) z[2 * q + 1] = (2 * q + 1 < db) ? rr[q] * sn[q] : 0.0;
-    }
-#pragma unroll
-    for (int e = 0; e < D; ++e) asm volatile("" : "+v"(z[e]));   // materialise the normals here
-}
-
 // ------------------------------------------------------------------------------------------------ random numbers drawn ahead
 // The mutation's draws depend only on (seed, particle id, stage, proposal index).  K1 keeps <= 64 of the 256 CUs busy while the
 // cloud is small, so the same launch carries extra blocks (behind the correction blocks in dispatch order) that draw the stage's
 // random numbers into zbuf on the idle CUs; K2 then loads D + 2 coalesced values per proposal instead of running Philox +
 // Box-Muller (~40 % of its arithmetic).  Layout: zbuf[(t ZS + slot) n + i], t = mh_step n_blocks + block, ZS = D + 2 slots:
-// MH uniform, mixture uniform, D normals.  Same expressions as draw2 -> same bits.
+// MH uniform, mixture uniform, D normals.  Drawn by mh_draw (kernels.hpp), like the draws inside the kernels -> same bits.
 struct Rng2 {
     double *zbuf;            // null: disabled
     int t_lim;               // > 0: only the first t_lim proposals (mh_step * n_blocks + block) of every particle are drawn
@@ -877,7 +838,7 @@ __device__ inline void rng2_block(const Geo2 &g, const Rng2 &ra, int n, int bloc
                 if (ra.t_lim > 0 && (int)t >= ra.t_lim) continue;
                 const int db = (b < ra.nb - 1) ? sub : ra.nf - sub * (ra.nb - 1);
                 double step_prob, uc, z[D];
-                draw2<D>(ra.seed, pid, (unsigned)n, t, db, debug, step_prob, uc, z);
+                mh_draw<D>(ra.seed, pid, (unsigned)n, t, db, step_prob, uc, z);
                 double *zt = ra.zbuf + (long long)t * (D + 2) * g.n + i;
                 zt[0] = step_prob;
                 zt[g.n] = uc;
@@ -1758,12 +1719,10 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
     return *s_fail == 0;
 }
 
-// LDS arrays of k2_mutate (ldslayout.hpp mut2: the mutation's, as in k_mutate_reg, then the prologue's scratch)
+// LDS arrays of k2_mutate (ldslayout.hpp mut2): the mutation body's (kernels.hpp MutBodyLds, as in k_mutate_reg), then the prologue's scratch
 template <int D>
-struct Mut2Lds {
+struct Mut2Lds : MutBodyLds<D> {
     static constexpr int DA = D + 1, NP = DA * (DA + 1) / 2, NPF = NP + 2;
-    double *Ls, *red, *m_lo, *m_hi, *m_a, *m_b, *m_k, *l_par, *l_dat, *Lraw, *logdet_s, *mub_raw, *sdd_raw, *sdn_raw;
-    int *m_fix, *m_fam, *bptr_s, *loff_s, *ball_raw;
     double *s_vt, *s_tot, *covl, *sig_f, *Aw, *Lw, *mean_s, *mu_f;
     int *bfree, *fi, *fi_j;
     // lik_data = false: no room for staged likelihood data (the generic mutation body of n_para > 10 reads its data where it is)
@@ -1774,13 +1733,7 @@ struct Mut2Lds {
     __device__ void place(double *sm) {
         using namespace lds;
         constexpr Mut2Layout O = mut2(D, 8, CAP);
-        Ls = lds_at<double, O[M_Ls]>(sm); red = lds_at<double, O[M_red]>(sm);
-        m_lo = lds_at<double, O[M_lo]>(sm); m_hi = lds_at<double, O[M_hi]>(sm); m_a = lds_at<double, O[M_a]>(sm); m_b = lds_at<double, O[M_b]>(sm);
-        m_k = lds_at<double, O[M_k]>(sm); l_par = lds_at<double, O[M_lpar]>(sm); l_dat = lds_at<double, O[M_ldat]>(sm); Lraw = lds_at<double, O[M_Lraw]>(sm);
-        logdet_s = lds_at<double, O[M_logdet]>(sm); mub_raw = lds_at<double, O[M_mub]>(sm); sdd_raw = lds_at<double, O[M_sddr]>(sm);
-        sdn_raw = lds_at<double, O[M_sdnr]>(sm);
-        m_fix = lds_at<int, O[M_fix]>(sm); m_fam = lds_at<int, O[M_fam]>(sm); bptr_s = lds_at<int, O[M_bptr]>(sm);
-        loff_s = lds_at<int, O[M_loff]>(sm); ball_raw = lds_at<int, O[M_ballr]>(sm);
+        this->template place_body<8, CAP>(sm);
         s_vt = lds_at<double, O[M_svt]>(sm); s_tot = lds_at<double, O[M_stot]>(sm);
         covl = lds_at<double, O[M_covl]>(sm); sig_f = lds_at<double, O[M_sigf]>(sm); Aw = lds_at<double, O[M_Aw]>(sm); Lw = lds_at<double, O[M_Lw]>(sm);
         mean_s = lds_at<double, O[M_mean]>(sm); mu_f = lds_at<double, O[M_muf]>(sm);
@@ -1873,31 +1826,11 @@ __device__ inline void k2_bookkeeping(DevState *st, Ctl2 *ctl, const Mut2Args &m
     if (tid < NWP) reinterpret_cast<double *>(&ctl->ps[n & 1])[tid] = reinterpret_cast<const double *>(&s_ps)[tid];
 }
 
-// The two likelihood descriptors as views for the mutation body; data that fits is staged in LDS (l_dat, LIK_LDS_CAP doubles) by the
-// whole block - the caller's next barrier publishes it.
-template <int T>
-__device__ inline void k2_stage_lik(const LikDev &ld0, const LikDev &ld1, double *l_par, double *l_dat, LikView (&lv)[2]) {
-    const int tid = threadIdx.x;
-    int used = 0;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const LikDev &ld = q == 0 ? ld0 : ld1;
-        const long long nd = ld.rows * ld.cols, na = ld.aux_rows * ld.aux_cols;
-        const bool fits = ld.family >= 0 && ld.family != SMCMI_LIK_CAPM_LITERAL && used + nd + na <= LIK_LDS_CAP;   // (capm_literal reads its data as scalars)
-        if (fits) {
-            for (long long k = tid; k < nd; k += T) l_dat[used + k] = ld.data[k];
-            for (long long k = tid; k < na; k += T) l_dat[used + nd + k] = ld.aux[k];
-        }
-        lv[q] = LikView{ld.family, l_par + q * LIK_PAR_MAX, ld.c0, fits ? l_dat + used : ld.data, ld.rows, ld.cols,
-                        fits ? l_dat + used + nd : ld.aux, ld.aux_rows, ld.aux_cols};
-        if (fits) used += (int)(nd + na);
-    }
-}
-
-// The MH steps of one particle (src/mutation.jl:86-138 over steps x blocks; helpers.jl:87-164 for alpha < 1): the body K2 and the
-// persistent segment kernel (stage3.hpp) share - same arithmetic in the same order.  The proposal's arrays are in LDS (L.Lraw,
-// L.logdet_s, L.mub_raw, L.sdd_raw, L.sdn_raw, L.ball_raw, L.bptr_s, L.loff_s), published by a barrier before the call; proposal 0's
-// random numbers may arrive in (step_prob, uc, z) (PREDRAW, or ma.zbuf).  ldz: leading dimension of ma.zbuf.  All threads call.
+// The MH steps of one particle (src/mutation.jl:86-138 over steps x blocks; helpers.jl:87-164 for alpha < 1): the loop K2, k2b_mutate and
+// the persistent segment kernel (stage3.hpp) share; every proposal in it is kernels.hpp's mh_draw + mh_step, as in engine 1's
+// k_mutate_reg.  The proposal's arrays are in LDS (L.Lraw, L.logdet_s, L.mub_raw, L.sdd_raw, L.sdn_raw, L.ball_raw, L.bptr_s, L.loff_s),
+// published by a barrier before the call; proposal 0's random numbers may arrive in (step_prob, uc, z) (PREDRAW, or ma.zbuf).  ldz: leading
+// dimension of ma.zbuf.  All threads call.
 // FAST (α = 1 only): A1F_LS - with one block L.Ls holds the expanded factor already (proposal2<.., FAST>); A1F_LOGDET - L.logdet_s is not
 // written: each wavefront forms the block's log-determinant from the diagonal of L.Lraw, the operations of proposal2 in their order (log of
 // each diagonal entry, added in ascending index from 0.0, times 2)
@@ -1911,7 +1844,6 @@ SMCMI_FP_CONTRACT
     const double c_alpha = ma.alpha;
     double *Ls = L.Ls, *Lraw = L.Lraw, *logdet_s = L.logdet_s, *mub_raw = L.mub_raw, *sdd_raw = L.sdd_raw, *sdn_raw = L.sdn_raw;
     int *bptr_s = L.bptr_s, *loff_s = L.loff_s, *ball_raw = L.ball_raw;
-    auto XN = [&](int k) { return x[k]; };
     const MixDense<D> MX(mixbuf, mixpos);
     double *Wraw = mixbuf + (ALPHA1 ? 0 : MixDense<D>::DOUBLES);
     if constexpr (!ALPHA1) mix_invert_factors<D, T>(Lraw, Wraw, loff_s, bptr_s, nb, tid);     // (prologue / pre-load ended with a barrier)
@@ -1921,14 +1853,8 @@ SMCMI_FP_CONTRACT
             const int p0 = bptr_s[b], db = bptr_s[b + 1] - p0;
             if ((nb > 1 || step == 0) && !((FAST & A1F_LS) != 0 && nb == 1)) {              // expand this block's constants to the padded D x D form
                 const double *Lb = Lraw + loff_s[b];
-                if constexpr (ALPHA1) {
-                    for (int e = tid; e < D * D; e += T) Ls[e] = 0.0;
-                    __syncthreads();
-                    for (int e = tid; e < db * db; e += T) {
-                        const int r = e / db, cidx = e % db;
-                        if (cidx <= r) Ls[cidx * D + ball_raw[p0 + r]] = Lb[r * db + cidx];   // transposed: Ls[e][k] = M[k][e]
-                    }
-                } else
+                if constexpr (ALPHA1) expand_alpha1_factor<D>(Ls, Lb, ball_raw + p0, db, T, tid);
+                else
                     mix_expand<D, T>(MX, Lb, Wraw + loff_s[b], ball_raw + p0, mub_raw + p0, sdd_raw + p0, sdn_raw + p0, db, logdet_s[b], tid);
                 __syncthreads();
             }
@@ -1953,62 +1879,9 @@ SMCMI_FP_CONTRACT
 #pragma unroll
                     for (int e = 0; e < D; ++e) z[e] = zt[(long long)(2 + e) * ldz];
                 }
-            } else if (!PREDRAW || t != 0) draw2<D>(ma.seed, pid, stage, t, db, ma.debug, step_prob, uc, z);   // (proposal 0 may have been drawn ahead of the prologue)
-            double prior_new = SMCMI_NEG_INF, like_new = SMCMI_NEG_INF, like_old_data = SMCMI_NEG_INF;
-            double q0 = 0.0, q1 = 0.0;
-            double xo[D];
-            if constexpr (ALPHA1) {
-                double zz2 = 0.0;
-#pragma unroll
-                for (int e = 0; e < D; ++e) zz2 += z[e] * z[e];
-                double logdet_b;
-                if constexpr ((FAST & A1F_LOGDET) != 0) logdet_b = logdet_w; else logdet_b = logdet_s[b];
-                q1 = (-((double)db * LOG2PI + logdet_b + zz2) / 2.0 < -745.1332191019412) ? __builtin_nan("") : 0.0;
-                double sacc[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) { xo[k] = x[k]; sacc[k] = 0.0; }
-#pragma unroll
-                for (int e = 0; e < D; ++e) {
-#pragma unroll
-                    for (int k = 0; k < D; ++k) sacc[k] += Ls[e * D + k] * z[e];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) asm volatile("" : "+v"(sacc[k]));
-                }
-#pragma unroll
-                for (int k = 0; k < D; ++k) x[k] = xo[k] + sacc[k];
-                if (ma.debug & 2) { prior_new = lprior - 0.1 * zz2; like_new = like - 0.2; like_old_data = 0.0; }
-                else if (in_bounds_s<D>(mv, XN)) {
-                    prior_new = logprior_s<D>(mv, XN, has_other);
-                    like_new = loglik_s<D>(lv[0], XN);
-                    if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
-                    like_old_data = (lv[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik_s<D>(lv[1], XN);
-                }
-            } else {
-            // mixture draw + proposal densities in parameter order (mix_propose, kernels.hpp): no gather / scatter, no division
-            double zz2 = 0.0;
-#pragma unroll
-            for (int e = 0; e < D; ++e) zz2 += z[e] * z[e];
-            double xn[D];
-            q0 = mix_propose<D, T>(MX, x, z, uc, c_alpha, (ma.debug & 4) != 0, mixzt + tid, xn);       // q0 - q1 as one number
-#pragma unroll
-            for (int k = 0; k < D; ++k) { xo[k] = x[k]; x[k] = xn[k]; }
-            if (ma.debug & 2) { prior_new = lprior - 0.1 * zz2; like_new = like - 0.2; like_old_data = 0.0; }
-            else if (in_bounds_s<D>(mv, XN)) {
-                prior_new = logprior_s<D>(mv, XN, has_other);
-                like_new = loglik_s<D>(lv[0], XN);
-                if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
-                like_old_data = (lv[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik_s<D>(lv[1], XN);
-            }
-            }
-            const double eta = exp(phi_n * (like_new - like) + (1.0 - phi_n) * (like_old_data - like_prev) +
-                                   (prior_new - lprior) + (q0 - q1));
-            if (step_prob < eta) {
-                like = like_new; lprior = prior_new; like_prev = like_old_data;
-                accept += (double)db;
-            } else {
-#pragma unroll
-                for (int k = 0; k < D; ++k) x[k] = xo[k];
-            }
+            } else if (!PREDRAW || t != 0) mh_draw<D>(ma.seed, pid, stage, t, db, step_prob, uc, z);   // (proposal 0 may have been drawn ahead of the prologue)
+            mh_step<D, ALPHA1, T>(Ls, (FAST & A1F_LOGDET) != 0 ? logdet_w : logdet_s[b], db, MX, lv, mv, has_other, ma.debug, c_alpha, phi_n, mixzt + tid, z, uc,
+                                  step_prob, x, like, lprior, like_prev, accept);
         }
     }
 }
@@ -2057,7 +1930,7 @@ __device__ inline void k2_mut_row(double *row, bool adaptive, double like, doubl
     k2_mut_row_f<T>(adaptive, like, like_prev, w_part, acc_val, e_center, live, rs, scratch, red, [&](int idx, double v) { row_store(row + idx, v, coh); }, e_base);
 }
 
-// K2.  The mutation body is k_mutate_reg's (src/mutation.jl:56-138, helpers.jl:87-164; same arithmetic in the same order), fed
+// K2.  The MH move is k_mutate_reg's (kernels.hpp mh_draw / mh_step: src/mutation.jl:56-138, helpers.jl:87-164), fed
 // from LDS by the prologue instead of from DevState; it reads the particle from buffer 0 (buffer 1 on resample stages: the
 // gathered cloud) and always writes buffer 0, applies normalize_weights! (particle.jl:362-366: W̃ N / ΣW̃, two roundings; 1 after a
 // resample) to the weight column and its history, and leaves one row of RMUT sums for the next stage's begin.
@@ -2092,7 +1965,7 @@ SMCMI_FP_CONTRACT
     wt_i = ma.wt[il];
     ModelView mv{D, L.m_fix, L.m_fam, L.m_lo, L.m_hi, L.m_a, L.m_b, L.m_k};
     LikView lv[2];
-    k2_stage_lik<T>(ld0, ld1, L.l_par, l_dat, lv);
+    stage_lik(ld0, ld1, L.l_par, l_dat, T, lv);
     // ---- the first proposal's random numbers depend on (seed, particle, stage) only: drawing them here puts ~40 % of the mutation's
     // arithmetic under the latency of the loads above and of the prologue's row totals
     // (512-thread blocks only: with 3 wavefronts per SIMD the 168-register budget has no room to carry them across the prologue)
@@ -2104,7 +1977,7 @@ SMCMI_FP_CONTRACT
         uc = zt[g.n];
 #pragma unroll
         for (int e = 0; e < D; ++e) z[e] = zt[(long long)(2 + e) * g.n];
-    } else if constexpr (PREDRAW) draw2<D>(ma.seed, pid, (unsigned)n, 0u, nb == 1 ? nf : (nf + nb - 1) / nb, ma.debug, step_prob, uc, z);
+    } else if constexpr (PREDRAW) mh_draw<D>(ma.seed, pid, (unsigned)n, 0u, nb == 1 ? nf : (nf + nb - 1) / nb, step_prob, uc, z);
     int rs = 0;
     double phi_n, e_center, nrm_sumw;
     if (ma.pre) {

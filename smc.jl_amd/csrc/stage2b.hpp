@@ -110,7 +110,7 @@ SMCMI_FP_CONTRACT
     for (int e = 0; e < D; ++e) z[e] = 0.0;
     ModelView mv{D, L.m_fix, L.m_fam, L.m_lo, L.m_hi, L.m_a, L.m_b, L.m_k};
     LikView lv[2];
-    k2_stage_lik<T>(ld0, ld1, L.l_par, l_dat, lv);
+    stage_lik(ld0, ld1, L.l_par, l_dat, T, lv);
     __syncthreads();
     // (development stamps, SMCMI_PROF2=<stage>: [1, 2] Prop2Glob + particle + likelihood data in, [8, 9] MH steps, [9, 10] stores + row, [10, 11] tail)
     for (int q = 2; q <= 8; ++q) K2_STAMP(ma.prof, q);

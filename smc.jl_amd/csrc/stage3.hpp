@@ -410,9 +410,9 @@ static __global__ void __launch_bounds__(T3, 2) k3_census(int *tick, unsigned lo
 
 // (MIX = false, α = 1: the mixture-component uniform is never read, so its Philox call is not made at all)
 template <int D, bool MIX = true>
-__device__ inline void k3_draw_park(double *z_park, unsigned long long seed, unsigned long long pid, unsigned stage, int db, int debug) {
+__device__ inline void k3_draw_park(double *z_park, unsigned long long seed, unsigned long long pid, unsigned stage, int db) {
     double step_prob, uc, z[D];
-    draw2<D>(seed, pid, stage, 0u, db, debug, step_prob, uc, z);
+    mh_draw<D>(seed, pid, stage, 0u, db, step_prob, uc, z);
     double *p = z_park + threadIdx.x;
     p[0] = step_prob;
     if constexpr (MIX) p[T3] = uc;
@@ -817,7 +817,7 @@ __device__ inline bool k3_rides(const RunParams &rp, const Seg3Args &sa, const P
 // discarded by `if constexpr`), and - unlike lambdas, whose by-reference captures put a dozen loop variables into scratch - they cost nothing.
 #define K3_DO_DRAW(ns)                                                                                                                          \
     do {                                                                                                                                        \
-        if ((ns) <= sa.n_last) k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid_park, (unsigned)(ns), db0, ma.debug);                               \
+        if ((ns) <= sa.n_last) k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid_park, (unsigned)(ns), db0);                               \
         K3_STAMP(sa.prof, 7);                                                                                                                   \
     } while (0)
 // po_p: Post2 of stage ns - 1; pair: stage ns's correction row is out as well (riding) - both tables' totals in one fetch, s_tot filled for the
@@ -1145,9 +1145,9 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     for (int k = tid; k < 2 * LIK_PAR_MAX; k += T3) L.l_par[k] = md->lik[k / LIK_PAR_MAX].par[k % LIK_PAR_MAX];
     ModelView mv{D, L.m_fix, L.m_fam, L.m_lo, L.m_hi, L.m_a, L.m_b, L.m_k};
     LikView lv[2];
-    k2_stage_lik<T3>(ma.lik[0], ma.lik[1], L.l_par, L.l_dat, lv);     // once per segment (the mutation rows' scratch is `red`, not this area)
+    stage_lik(ma.lik[0], ma.lik[1], L.l_par, L.l_dat, T3, lv);     // once per segment (the mutation rows' scratch is `red`, not this area)
     const int db0 = nb == 1 ? nf : (nf + nb - 1) / nb;          // entries of the first random block
-    k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid_park, (unsigned)n, db0, ma.debug);      // (later stages: under the wait for their begin)
+    k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid_park, (unsigned)n, db0);      // (later stages: under the wait for their begin)
     __syncthreads();
     int done = 0;
     bool timed_out = false;
@@ -1273,7 +1273,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             for (int k = 0; k < D; ++k) x[k] = stx[k * T3 + tid];
             like = sto[T3 + tid]; lprior = sto[2 * T3 + tid]; like_prev = sto[3 * T3 + tid]; acc_val = sto[4 * T3 + tid];
             // this stage's draws again (the parking area was the selection's scratch; they are functions of (seed, particle, stage))
-            k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid, (unsigned)n, db0, ma.debug);
+            k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid, (unsigned)n, db0);
             __syncthreads();
             rs = 1; dec = 0;
         }
@@ -1294,7 +1294,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             for (int k = 0; k < D; ++k) x[k] = tr[(5 + k) * T3 + tid];
             like = tr[T3 + tid]; lprior = tr[2 * T3 + tid]; like_prev = tr[3 * T3 + tid]; acc_val = tr[4 * T3 + tid];
             // chunk 0's draws of this stage again (the parking area was the selection's scratch)
-            k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid_park, (unsigned)n, db0, ma.debug);
+            k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid_park, (unsigned)n, db0);
             __syncthreads();
             rs = 1; dec = 0;
         }
@@ -1342,7 +1342,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             uc = p[T3];
 #pragma unroll
             for (int e = 0; e < D; ++e) z[e] = p[(2 + e) * T3];
-        } else draw2<D>(ma.seed, pid, (unsigned)n, 0u, db0, ma.debug, step_prob, uc, z);       // (only chunk 0's first proposal is drawn ahead)
+        } else mh_draw<D>(ma.seed, pid, (unsigned)n, 0u, db0, step_prob, uc, z);       // (only chunk 0's first proposal is drawn ahead)
         if (live) {
             Wt = rs ? 1.0 : (v * nrm_N) / nrm_sumw;             // W·N then /ΣW̃, two roundings like the reference (particle.jl:362-366); 1 after a resample
             if (ma.hist_W && ma.store_history) ma.hist_W[(long long)(n - 1) * ma.hist_ld + i] = Wt;

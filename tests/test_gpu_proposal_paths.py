@@ -173,8 +173,8 @@ def test_other_proposal_paths_keep_their_bits(name, segments, launches):
 
 @pytest.mark.parametrize("name", FLAT_IDS)
 def test_log_determinant_decides_the_underflow_quirk_as_the_oracle(name, segments, launches, oracle_run):
-    """-(d log 2π + log det + |z|²) / 2 < -745.13: the proposal density underflows in the reference and the move is rejected (stage2.hpp
-    k2_mh_steps).  Oracle acceptance after the first record (N = 20 000): s = 1e30 ordinary (1.0, 0.40, 0.35, ...); s = 1.5e32: 0.05, 0.09, 0.17,
+    """-(d log 2π + log det + |z|²) / 2 < -745.13: the proposal density underflows in the reference and the move is rejected (kernels.hpp
+    mh_step).  Oracle acceptance after the first record (N = 20 000): s = 1e30 ordinary (1.0, 0.40, 0.35, ...); s = 1.5e32: 0.05, 0.09, 0.17,
     0.20, 0.18 - the particles with large |z|², a log-determinant off by one moves these by several points; s = 1e40: exactly 0 everywhere."""
     a, b, r = segments[name], launches[name], oracle_run(name)
     n, s = CASES[name]["n"], CASES[name]["flat_s"]
