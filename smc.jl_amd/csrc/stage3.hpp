@@ -389,6 +389,140 @@ __device__ inline bool gather_totals_pair(const unsigned long long *tbl_m, unsig
     return true;
 }
 
+// ---- the hand-overs of the two-hand-over, one-handle, one-chunk segment (inst3 / inst3m: the headline's kind), -DSMCMI_K3HO=<bits>.  Each
+// bit moves WHEN a word is looked at, WHICH code fetches it or WHERE a value waits - never an operation, or the order of operations, on a
+// value that reaches a result.  In every other translation unit (riding, two chunks, several handles) K3HO is 0 and the kernel's text is the
+// one it was.
+#define K3H_FETCH 1               // the V totals of a hand-over through k3_totals (below) instead of gather_totals
+#define K3H_SW 2                  // the schedule window of stage n + 1's begin is filled behind stage n's Post2, under the hand-over, not in begin_stage
+#define K3H_REDRAW 4              // a stage that resampled inside the segment draws its parked random numbers again UNDER the selection's second hand-over, not behind it
+#ifndef SMCMI_K3HO
+#define SMCMI_K3HO (K3H_FETCH | K3H_SW | K3H_REDRAW)
+#endif
+#if defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1 && SMCMI_INST3_A != 0
+#define K3HO (SMCMI_K3HO)
+#elif defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1
+// (the mixture kernel: with the redraw inside k3_select_inside its scratch grows from 64 to 80 bytes per lane at n_para 10, past the bound
+// tests/test_abi_cpu.py holds it to; its redraw stays where it was)
+#define K3HO ((SMCMI_K3HO) & ~K3H_REDRAW)
+#else
+#define K3HO 0
+#endif
+// What a launch's calls of k3_totals have in common: written once in the launch's prologue, in LDS - a call moves one LDS address and a tag
+// (gather_totals' eleven arguments were ~90 lane reads and ~150 scalar instructions at every call site, on the chain each time).
+#define K3_GLOBAL __attribute__((address_space(1)))
+#define K3_LDS __attribute__((address_space(3)))
+struct K3Ho {
+    const unsigned long long *tbl[2];      // the table every block takes its totals from: [0] correction, [1] mutation (the workers' rows where a shard is one block)
+    unsigned long long *to;                // time-out flag words
+    K3_LDS double *tot, *vt;               // the totals [m]; the shard values [V2_MAXV][m]
+    K3_LDS int *s_to;                      // the block's time-out flag
+    int nvs;
+};
+// gather_totals<1> for ONE launch-invariant table of a one-handle segment: the same polls, the same fetch with every tag checked, the same
+// sums in the same order (0 + x_0 + x_1 + ... over the shards, the maximum for MAXI), with
+//   * M, MAXI and the table (KIND) compile-time, T3 for blockDim.x (whose read - a scalar load, a global load and a full vmcnt(0) - stood
+//     between the barrier and the first addition);
+//   * the polled words and the time-out words addressed as global memory and the staging area as LDS (generic pointers made every probe a
+//     flat load, counted on both wait counters, and every LDS access a flat access);
+//   * agent scope only, no vt_out;
+//   * the final sum with every shard value loaded from LDS before the first addition (V = 8, the headline's, fully unrolled; other V in a
+//     loop), and where a column takes the maximum the sum and the maximum as two independent chains - every lane keeps the one that is its own.
+// Out of line like gather_totals (inlined, a wider fetch cost the stage loop 14 spilled registers: round 6).  All threads call; false: timed out.
+template <int M, int MAXI, int KIND>
+__device__ __attribute__((noinline)) bool k3_totals(const K3Ho *hp_, unsigned tag_) {
+    static_assert(M <= 128 && M <= T3, "two fetches per lane, one column per thread");
+    const K3_LDS K3Ho *hp = (const K3_LDS K3Ho *)hp_;
+    auto uni64 = [](unsigned long long a) __attribute__((always_inline)) {
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+        return ((unsigned long long)hi << 32) | lo;
+    };
+    const unsigned tag = __builtin_amdgcn_readfirstlane(tag_);
+    const K3_GLOBAL unsigned long long *tbl = (const K3_GLOBAL unsigned long long *)uni64((unsigned long long)hp->tbl[KIND]);
+    K3_GLOBAL unsigned long long *to = (K3_GLOBAL unsigned long long *)uni64((unsigned long long)hp->to);
+    K3_LDS double *tot = hp->tot, *vt = hp->vt;
+    K3_LDS int *s_to = hp->s_to;
+    const int nvs = __builtin_amdgcn_readfirstlane(hp->nvs);
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    if (w < nvs) {                                                          // (wave-uniform)
+        const K3_GLOBAL unsigned long long *row = tbl + (long long)w * M * 2;
+        // (the paced poll of the first word comes first: gather_totals)
+        if (lane == 0) {
+            unsigned long long a = __hip_atomic_load(row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((unsigned)(a >> 32) != tag) {
+                const long long t0 = wall_clock64();
+                const long long lim = (long long)__hip_atomic_load(to + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                do {
+                    __builtin_amdgcn_s_sleep(1);
+                    a = __hip_atomic_load(row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if ((unsigned)(a >> 32) == tag) break;
+                    if (wall_clock64() - t0 > lim || __hip_atomic_load(to, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                        __hip_atomic_store(to, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        *s_to = 1;
+                        break;
+                    }
+                } while (true);
+            }
+        }
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(unsigned long long)row, 0, M * 16, 0x00020000);
+        const long long t_begin = wall_clock64();
+        constexpr int NQ = M > 64 ? 2 : 1;
+        for (;;) {
+            int bad = 0;
+            u32x4_t xs[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int k = lane + 64 * q;
+                xs[q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (k < M ? k : M - 1) * 16, 0, 16);
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int k = lane + 64 * q;
+                // (every lane checks the granule it fetched - beyond M that is column M - 1 again - so that no fetch is sunk into the branch below and
+                // both are in flight together)
+                bad |= (xs[q].y != tag) | (xs[q].w != tag);
+                if (k < M) vt[w * M + k] = __hiloint2double((int)xs[q].z, (int)xs[q].x);
+            }
+            if (!__any(bad)) break;
+            // a word was not there yet: fetch again, bounded like every other wait (another wavefront's time-out ends this one too)
+            if (*(volatile K3_LDS int *)s_to) break;
+            if (lane == 0 && (wall_clock64() - t_begin > (long long)__hip_atomic_load(to + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
+                              __hip_atomic_load(to, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                __hip_atomic_store(to, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                *s_to = 1;
+            }
+            if (*(volatile K3_LDS int *)s_to) break;
+            __builtin_amdgcn_s_sleep(4);
+        }
+    }
+    __syncthreads();
+    if (*s_to) return false;
+    const int k = threadIdx.x;
+    if (k < M) {
+        const double ninf = -__builtin_inf();
+        double ta = 0.0, tm = ninf;
+        if (nvs == 8) {
+            double x[8];
+#pragma unroll
+            for (int v = 0; v < 8; ++v) x[v] = vt[v * M + k];
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                ta = ta + x[v];
+                if constexpr (MAXI >= 0) tm = fmax(tm, x[v]);
+            }
+        } else {
+            for (int v = 0; v < nvs; ++v) {
+                const double xv = vt[v * M + k];
+                ta = ta + xv;
+                if constexpr (MAXI >= 0) tm = fmax(tm, xv);
+            }
+        }
+        tot[k] = (MAXI >= 0 && k == MAXI) ? tm : ta;
+    }
+    __syncthreads();
+    return true;
+}
+
 // Residency self-test of a handle's segment geometry (first use): `grid` blocks of T3 threads with enough LDS that a CU holds ONE of
 // them - the strictest placement the segment kernel can get - take a ticket; the last publishes a granule every block waits for
 // (bounded).  ok counts the blocks that saw it: anything but `grid` (or a raised time-out flag) keeps the handle on engine 2.
@@ -530,11 +664,19 @@ __device__ inline void k3_leave_note(const Seg3Args &sa, const Ctl2 *ctl) {
 // rows.  Two more hand-overs: "every particle and cum value is written" (no payload), and the moment rows of the resampled cloud.
 // Not inlined, and the particle comes and goes through LDS (stx: [θ_1..θ_D][T3], sto: [W̃ | loglh | logprior | old_loglh | accept][T3]): the
 // stage loop keeps its registers.  sc: the workers' parking area as scratch.  Returns 1 when a wait timed out.
-template <int D>
+#if (K3HO) & K3H_REDRAW
+#define K3_SEL_DB_PARAM , int db
+#define K3_SEL_TPARAMS template <int D, bool MIXDRAW>
+#else
+#define K3_SEL_DB_PARAM
+#define K3_SEL_TPARAMS template <int D>
+#endif
+K3_SEL_TPARAMS
 __device__ __attribute__((noinline)) int k3_select_inside(const Sel3Args *selp, double *buf0, long long cl_n, int cl_R, long long Ng, int nchunks, int V, int rowi, long long i,
                                                           long long beg, long long end, unsigned tag, int n, unsigned long long seed, long long gid0,
                                                           const unsigned long long *g_cm, unsigned long long *to, int *s_to, double *s_tot, double *s_vt, double *s_sw,
-                                                          double *red, double *sc, double *stx, double *sto, const double *shift, long long *pf, bool rows_direct, bool rows_two) {
+                                                          double *red, double *sc, double *stx, double *sto, const double *shift, long long *pf, bool rows_direct, bool rows_two
+                                                          K3_SEL_DB_PARAM) {
 #define K3S(k) do { if (pf && threadIdx.x == 0) pf[k] = wall_clock64(); } while (0)
     constexpr int NPm = Mut2Lds<D>::NP, MGM = pad2(NPm), DAm = D + 1, NPF = Mut2Lds<D>::NPF, MCM = pad2(NPF);
     const Sel3Args sl = *selp;
@@ -673,6 +815,12 @@ __device__ __attribute__((noinline)) int k3_select_inside(const Sel3Args *selp, 
     }, [&](int idx, double val) { gran_store(my_gm + idx * 2, val, tag); });
     if (tid >= NPm && tid < MGM) gran_store(my_gm + tid * 2, 0.0, tag);
     K3S(8);
+#if (K3HO) & K3H_REDRAW
+    // the stage's draws again (functions of (seed, particle, stage); the parking area was this selection's scratch), under the wait for the
+    // moment totals.  The scratch is free: its last readers - the searches of step (5) - lie in front of the moment row's barriers, and every
+    // thread writes the slots it alone reads.  The particle in transit (stx, sto) lies behind the parking area (ldslayout.hpp seg3) or in device memory.
+    k3_draw_park<D, MIXDRAW>(sc, seed, (unsigned long long)(gid0 + i), (unsigned)n, db);
+#endif
     if (!(rows_two ? gather_totals<2>(sl.g_gm, V, MGM, -1, tag, to, s_to, s_tot + 2, s_vt)
                    : gather_totals(sys ? sl.mine + sl.off_gm : (rows_direct ? sl.g_gm : sl.gt_gm), V, MGM, -1, tag, to, s_to, s_tot + 2, s_vt, sys))) return 1;
     K3S(9);
@@ -834,7 +982,7 @@ __device__ inline bool k3_rides(const RunParams &rp, const Seg3Args &sa, const P
                                                 (writer && sys) ? sa.vt_mut_out : nullptr);                                                     \
         } else {                                                                                                                                \
             ok_ = rows_two ? gather_totals<2>(sa.g_mut + K3_RPAR((ns) - 1), g.V, RMUT, RMAX_IDX, tag_p_, sa.to, &s_to, s_tot, s_vt)            \
-                           : gather_totals(rows_direct ? sa.g_mut + K3_RPAR((ns) - 1) : sa.gt_mut + K3_TPAR((ns) - 1), g.V, RMUT, RMAX_IDX, tag_p_, sa.to, &s_to, s_tot, s_vt, sys,  \
+                           : K3_TOTALS_MUT(rows_direct ? sa.g_mut + K3_RPAR((ns) - 1) : sa.gt_mut + K3_TPAR((ns) - 1), tag_p_,                 \
                                            (writer && sys) ? sa.vt_mut_out : nullptr);                                                          \
         }                                                                                                                                       \
         if (!ok_) { timed_out = true; ACT = -1; break; }                                                                                        \
@@ -845,6 +993,31 @@ __device__ inline bool k3_rides(const RunParams &rp, const Seg3Args &sa, const P
         if (ACT == 0 && writer && tid < NWB_) reinterpret_cast<double *>(&ctl->bg)[tid] = reinterpret_cast<const double *>(&s_a.bg)[tid];       \
         K3_STAMP(sa.prof, 9);                                                                                                                   \
     } while (0)
+// the V totals of a hand-over where every block of a launch takes them from the same table: through k3_totals (K3H_FETCH: the table is in s_ho)
+// or gather_totals<1> as ever
+#if (K3HO) & K3H_FETCH
+#define K3_TOTALS_CM(tbl_, tag_) k3_totals<MCM, -1, 0>(&s_ho, (tag_))
+#define K3_TOTALS_MUT(tbl_, tag_, out_) k3_totals<RMUT, RMAX_IDX, 1>(&s_ho, (tag_))
+#else
+#define K3_TOTALS_CM(tbl_, tag_) gather_totals((tbl_), g.V, MCM, -1, (tag_), sa.to, &s_to, s_tot, s_vt, sys)
+#define K3_TOTALS_MUT(tbl_, tag_, out_) gather_totals((tbl_), g.V, RMUT, RMAX_IDX, (tag_), sa.to, &s_to, s_tot, s_vt, sys, (out_))
+#endif
+// K3H_SW: the window of the proposed schedule begin_stage(n + 1) walks depends on Post2::j of stage n alone, which is final with the stage's
+// post2 - a proposal, an MH step and a hand-over in front of that begin.  It is filled there (the workers behind their mutation row, the
+// gatherers behind their post2), so its load from the schedule runs under the hand-over instead of in front of the Newton predictor that
+// needs it.  Wavefront 0 writes and reads it, in program order.  Nothing else touches s_sw in between: the in-segment selection, the only
+// other user (its "everything is written" totals), takes it as scratch in FRONT of the stage's post2, that is behind the begin that read it.
+#if (K3HO) & K3H_SW
+#define K3_FILL_SW(po_n_)                                                                                                                       \
+    do {                                                                                                                                        \
+        if (tid < 64) {                                                                                                                         \
+            const int jj_ = (po_n_).j - 1 + tid;                                                                                                \
+            s_sw[tid] = (!rp.use_fixed_schedule && jj_ >= 0 && jj_ < rp.n_phi) ? sa.sched[jj_] : 2.0;                                           \
+        }                                                                                                                                       \
+    } while (0)
+#else
+#define K3_FILL_SW(po_n_) (void)0
+#endif
 #define K3_RPAR(stage) ((RIDE && ((stage) & 1)) ? (long long)k3_copy_words(g.Vl * g.nb2) : 0)
 #define K3_TPAR(stage) ((RIDE && ((stage) & 1)) ? (sys ? (long long)MB_SEG_COPY_WORDS : (long long)k3_copy_words(g.Vl * g.nb2)) : 0)
 // TWO CHUNKS PER WORKER (k3_segment<D, true, RIDE, 2>) is compiled from this same kernel body in translation units of its own, which define
@@ -920,6 +1093,14 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
 #endif
     const bool worker = (int)blockIdx.x < W, writer = blockIdx.x == 0;
     if (tid == 0) { s_rp = st->rp; s_to = 0; }
+#if (K3HO) & K3H_FETCH
+    __shared__ K3Ho s_ho;                                       // (k3_totals: what its calls have in common)
+    if (tid == 64) {
+        const bool direct = g.nb2 == 1;                         // (rows_direct below: the workers take each other's rows, no gatherer runs)
+        s_ho.tbl[0] = direct ? sa.g_cm : sa.gt_cm; s_ho.tbl[1] = direct ? sa.g_mut : sa.gt_mut;
+        s_ho.to = sa.to; s_ho.tot = (K3_LDS double *)s_tot; s_ho.vt = (K3_LDS double *)s_vt; s_ho.s_to = (K3_LDS int *)&s_to; s_ho.nvs = g.V;
+    }
+#endif
     if (tid < nf) L.fi[tid] = md->free_inds[tid];
     __syncthreads();
     const RunParams &rp = s_rp;
@@ -966,10 +1147,12 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     // else begin2_wave's code (finished / paused / error / no usable prediction: the writer has set the status).  Ends with a barrier.
     auto begin_stage = [&](int nb_, const Post2 &po_n, const double *tm) -> int {
         if (tid == 0) s_act = 7;
+#if !((K3HO) & K3H_SW)
         if (tid < 64) {
             const int jj = po_n.j - 1 + tid;                    // the window of the proposed schedule the begin walks
             s_sw[tid] = (!rp.use_fixed_schedule && jj >= 0 && jj < rp.n_phi) ? sa.sched[jj] : 2.0;
         }
+#endif
         if (nb_ <= sa.n_last) {
             if (tid < 64) {
                 const int act = begin2_wave(nb_, po_n, rp, tm, tm[RMAX_IDX], true, 1, sa.sched, s_sw, &s_a.bg, &st->sol[0], writer, ma.rec,
@@ -1018,7 +1201,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
                 K3_WALL(sa.gprof, PROF2_GATH + 6 * vg + 1);
                 K3_WALL(sa.gprof, PROF2_GATH + 6 * vg + 2);
                 // the decision every worker takes from the V totals (a stage that does not go on mutates nothing: no rows to wait for)
-                if (!gather_totals(sa.gt_cm + tpar, g.V, MCM, -1, tag, sa.to, &s_to, s_tot, s_vt, sys)) break;
+                if (!K3_TOTALS_CM(sa.gt_cm + tpar, tag)) break;
             }
             const double ess = s_tot[0] * s_tot[0] / s_tot[1];
             int rs_g = entered ? rs0 : 0;
@@ -1046,6 +1229,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             }
             if (tid == 0) post2(n, s_a.bg, s_b[(n - 1) & 1].po, rp, s_tot[0], s_tot[1], ess, rs_g, &s_b[n & 1].po);
             __syncthreads();
+            K3_FILL_SW(s_b[n & 1].po);
             K3_WALL(sa.gprof, PROF2_GATH + 6 * vg + 3);
             if (!gather_vshard<T3>(sa.g_mut + rpar + (long long)vg * g.nb2 * RMUT * 2, g.nb2, RMUT, RMAX_IDX, tag, sa.to, &s_to,
                                    [&](int idx, double val) { post_total(sa.gt_mut + tpar, sa.off_mut + tpar, ((long long)(g.v0 + vg) * RMUT + idx) * 2, val, tag); }, g_stage,
@@ -1054,7 +1238,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             cm_posted = false;
             if (RIDE && k3_rides(rp, sa, s_b[n & 1].po, n, sys)) { if (!sweep_cm(n + 1)) break; cm_posted = true; }
             K3_WALL(sa.gprof, PROF2_GATH + 6 * vg + 5);
-            if (!gather_totals(sa.gt_mut + tpar, g.V, RMUT, RMAX_IDX, tag, sa.to, &s_to, s_tot, s_vt, sys)) break;
+            if (!K3_TOTALS_MUT(sa.gt_mut + tpar, tag, nullptr)) break;
             if (begin_stage(n + 1, s_b[n & 1].po, s_tot) != 0) break;
         }
         return;
@@ -1247,7 +1431,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         if constexpr ((FAST & A1F_SHUF) != 0) { if (tid >= 64 && tid < 128) shuffle_trace(jx_pre, tid - 64, nf, nb, L.bfree, L.bptr_s); }
         // ---- the V shard totals -> decision (smc_main.jl:427-455) -> proposal (smc_main.jl:457-465, helpers.jl:215-260, mutation.jl:81)
         if (!entered && !(RIDE && rides) && !(rows_two ? gather_totals<2>(sa.g_cm + K3_RPAR(n), g.V, MCM, -1, tag, sa.to, &s_to, s_tot, s_vt)
-                                   : gather_totals(rows_direct ? sa.g_cm + K3_RPAR(n) : sa.gt_cm + K3_TPAR(n), g.V, MCM, -1, tag, sa.to, &s_to, s_tot, s_vt, sys))) { timed_out = true; break; }
+                                   : K3_TOTALS_CM(rows_direct ? sa.g_cm + K3_RPAR(n) : sa.gt_cm + K3_TPAR(n), tag))) { timed_out = true; break; }
         K3_STAMP(sa.prof, 3);
         K3_WALL(sa.gprof, PROF2_WORK + 4 * blockIdx.x + 1);
         double ess = s_tot[0] * s_tot[0] / s_tot[1];
@@ -1266,14 +1450,22 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
 #pragma unroll
             for (int k = 0; k < D; ++k) stx[k * T3 + tid] = x[k];
             sto[T3 + tid] = like; sto[2 * T3 + tid] = lprior; sto[3 * T3 + tid] = like_prev; sto[4 * T3 + tid] = acc_val;
+#if (K3HO) & K3H_REDRAW
+            const int bad = k3_select_inside<D, !ALPHA1>(sa.sel, cl.buf[0], cl.n, cl.R, g.N, g.V * g.nb1, g.V, rowi, i, beg, end, tag, n, ma.seed, ma.gid0, sa.g_cm + K3_RPAR(n), sa.to, &s_to, s_tot, s_vt, s_sw,
+                                                red, z_park, stx, sto, po.shift, (sa.prof && writer && n == sa.prof_stage) ? sa.gprof + PROF2_SEL : nullptr, rows_direct, rows_two, db0);
+#else
             const int bad = k3_select_inside<D>(sa.sel, cl.buf[0], cl.n, cl.R, g.N, g.V * g.nb1, g.V, rowi, i, beg, end, tag, n, ma.seed, ma.gid0, sa.g_cm + K3_RPAR(n), sa.to, &s_to, s_tot, s_vt, s_sw,
                                                 red, z_park, stx, sto, po.shift, (sa.prof && writer && n == sa.prof_stage) ? sa.gprof + PROF2_SEL : nullptr, rows_direct, rows_two);
+#endif
             if (bad) { timed_out = true; break; }
 #pragma unroll
             for (int k = 0; k < D; ++k) x[k] = stx[k * T3 + tid];
             like = sto[T3 + tid]; lprior = sto[2 * T3 + tid]; like_prev = sto[3 * T3 + tid]; acc_val = sto[4 * T3 + tid];
             // this stage's draws again (the parking area was the selection's scratch; they are functions of (seed, particle, stage))
+            // (K3H_REDRAW: k3_select_inside has drawn them under its second hand-over)
+#if !((K3HO) & K3H_REDRAW)
             k3_draw_park<D, !ALPHA1>(z_park, ma.seed, pid, (unsigned)n, db0);
+#endif
             __syncthreads();
             rs = 1; dec = 0;
         }
@@ -1365,12 +1557,16 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         K3_WALL(sa.gprof, PROF2_WORK + 4 * blockIdx.x + 2);
         if constexpr (RIDE) rides = k3_rides(rp, sa, B.po, n, sys);             // stage n + 1's correction row goes out right behind this row?
         else {
+            K3_FILL_SW(B.po);
             K3_DO_DRAW(n + 1);                                  // stage n + 1's draws, under the hand-over
             K3_DO_BEGIN(n + 1, B.po, false, act);               // ---- the V shard totals -> stage n + 1's begin
             if (act != 0) break;                                // leave: registers hold the cloud after stage n
         }
     }
 #undef K3_RPAR
+#undef K3_FILL_SW
+#undef K3_TOTALS_CM
+#undef K3_TOTALS_MUT
 #undef K3_TPAR
 #undef K3_DO_DRAW
 #undef K3_DO_BEGIN
