@@ -396,8 +396,9 @@ __device__ inline bool gather_totals_pair(const unsigned long long *tbl_m, unsig
 #define K3H_FETCH 1               // the V totals of a hand-over through k3_totals (below) instead of gather_totals
 #define K3H_SW 2                  // the schedule window of stage n + 1's begin is filled behind stage n's Post2, under the hand-over, not in begin_stage
 #define K3H_REDRAW 4              // a stage that resampled inside the segment draws its parked random numbers again UNDER the selection's second hand-over, not behind it
+#define K3H_GATHER 8              // a gatherer's sweeps of the correction and the mutation rows through k3_gather (below) instead of gather_vshard
 #ifndef SMCMI_K3HO
-#define SMCMI_K3HO (K3H_FETCH | K3H_SW | K3H_REDRAW)
+#define SMCMI_K3HO (K3H_FETCH | K3H_SW | K3H_REDRAW | K3H_GATHER)
 #endif
 #if defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1 && SMCMI_INST3_A != 0
 #define K3HO (SMCMI_K3HO)
@@ -520,6 +521,191 @@ __device__ __attribute__((noinline)) bool k3_totals(const K3Ho *hp_, unsigned ta
         tot[k] = (MAXI >= 0 && k == MAXI) ? tm : ta;
     }
     __syncthreads();
+    return true;
+}
+
+// What a gatherer's sweeps of one launch have in common (K3H_GATHER), written once in the launch's prologue, in the gatherer's LDS: a call of
+// k3_gather moves one LDS address and a tag.  (These kernels do not ride: no stage-parity copies of the tables.)
+struct K3Gh {
+    const unsigned long long *tbl[2];      // this virtual shard's rows: [0] correction, [1] mutation
+    unsigned long long *dst[2];            // this virtual shard's slots in the two tables of shard totals
+    unsigned long long *to;                // time-out flag words
+    long long *pw;                         // SMCMI_PROF2: this gatherer's PROF2_GPOLL words (nullptr: none), written by the sweeps that carry ptag
+    K3_LDS double *stage;                  // the staging area [nr][M]
+    K3_LDS int *s_to;                      // the block's time-out flag
+    int nr;                                // rows of the shard
+    unsigned ptag;
+};
+constexpr int K3G_ROWS = 32;               // the most rows k3_gather takes
+// (33 .. GRP rows - one handle cut into 4, 2 or 1 virtual shards: the unchanged gather_vshard, out of line)
+template <int M, int MAXI, int KIND>
+__device__ __attribute__((noinline)) bool k3_gather_wide(const K3Gh *hp_, unsigned tag) {
+    const K3_LDS K3Gh *hp = (const K3_LDS K3Gh *)hp_;
+    unsigned long long *dst = hp->dst[KIND];
+    long long *pw = hp->pw;
+    return gather_vshard<T3>(hp->tbl[KIND], hp->nr, M, MAXI, tag, hp->to, (int *)hp->s_to,
+                             [&](int idx, double val) { gran_store(dst + idx * 2, val, tag); }, (double *)hp->stage,
+                             (pw && tag == hp->ptag) ? pw + 2 * KIND : nullptr);
+}
+// gather_vshard for ONE launch-invariant row table of a one-handle, one-chunk segment whose shard is at most 32 rows (every 8-shard geometry:
+// at most 31): the same polls of the rows' first words, the same fetch with every tag checked, the same additions in the same order (one
+// canonical group: slices 2h, 2h + 1 in ascending row order, the tree across the quad, 0 + group), with
+//   * M, MAXI and the table (KIND) compile-time, T3 for blockDim.x, the table, the time-out words and the posted words addressed as global
+//     memory, the staging area and the time-out flag as LDS;
+//   * the rows fetched AS THEY LAND: wavefront w owns rows w, w + 8, w + 16, w + 24 - one lane per owned row makes the paced poll of the row's
+//     first word (kept in front of the fetch: sweeping as the probe queues the sweeps in front of the workers' row stores, gather_vshard), then
+//     the wavefront fetches its rows' granules, consecutive lanes consecutive granules, every load in flight together; every lane checks
+//     the tags of what it fetched (beyond the wavefront's last granule that is the last granule again: no load is sunk behind another's
+//     wait); a fetch that meets a missing word repeats, paced and bounded, by that wavefront alone (another wavefront's time-out ends it).
+//     No block barrier between poll and fetch; ONE in front of the reduction;
+//   * the reduction's loop over the rows PRESENT, in whole steps of 8 rows (1 .. 4 steps, each count a text of its own with all of a thread's
+//     LDS loads in front of its first addition), not over GRP = 64 row slots.  The steps left out add only the identity to every chain, and
+//     adding it changes no bit: a sum chain starts as +0.0 + x, which is never -0.0 (+0.0 + -0.0 = +0.0 when rounding to nearest), and a sum
+//     of two values of which one is not -0.0 is not -0.0 either (exact cancellation gives +0.0) - so the accumulator a is never -0.0 and
+//     a + 0.0 = a, also for an infinity or a NaN (already quiet: it is the result of an addition).  A maximum chain starts as
+//     fmax(-inf, x), which is never a NaN (fmax returns its other argument), so fmax(a, -inf) = a.  The rows missing from the LAST step
+//     present still add the identity, as before;
+//   * where a column takes the maximum (MAXI), sum and maximum as two chains: every thread keeps the one that is its column's;
+//   * the thread that ends up with totals 2 pr, 2 pr + 1 writes their four tagged words - 32 contiguous, 16-byte-aligned bytes - as two
+//     16-byte buffer stores with gran_store's agent scope (sc1), issued back to back.  A reader checks both tags of every granule.
+// The staging area is written without a barrier at the function's head: between two sweeps of a gatherer stands at least the barrier of
+// the fetch of the totals (k3_totals / gather_totals), so no thread still reads the previous sweep's rows.  All threads call; false: timed out.
+template <int M, int MAXI, int KIND>
+__device__ __attribute__((noinline)) bool k3_gather(const K3Gh *hp_, unsigned tag_) {
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    constexpr int NW = T3 / 64, RW = 32 / NW, U = (RW * M + 63) / 64;      // wavefronts; rows per wavefront at most; granules per lane at most
+    static_assert(M % 2 == 0 && 2 * M <= T3 && NW * RW == K3G_ROWS, "a quad of threads per pair of columns, 32 rows over the block's wavefronts");
+    const K3_LDS K3Gh *hp = (const K3_LDS K3Gh *)hp_;
+    const int nr = __builtin_amdgcn_readfirstlane(hp->nr);                  // (<= K3G_ROWS: the call site's dispatch, K3_GATHER)
+    auto uni64 = [](unsigned long long a) __attribute__((always_inline)) {
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+        return ((unsigned long long)hi << 32) | lo;
+    };
+    const unsigned tag = __builtin_amdgcn_readfirstlane(tag_);
+    const K3_GLOBAL unsigned long long *tbl = (const K3_GLOBAL unsigned long long *)uni64((unsigned long long)hp->tbl[KIND]);
+    K3_GLOBAL unsigned long long *to = (K3_GLOBAL unsigned long long *)uni64((unsigned long long)hp->to);
+    K3_GLOBAL unsigned long long *dst = (K3_GLOBAL unsigned long long *)uni64((unsigned long long)hp->dst[KIND]);
+    K3_LDS double *stage = hp->stage;
+    K3_LDS int *s_to = hp->s_to;
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int nrw = w < nr ? (nr - w + NW - 1) / NW : 0;                    // rows w, w + NW, ... of this wavefront
+    int fetches = 0;
+    if (nrw > 0) {                                                          // (wave-uniform)
+        if (lane < nrw) {
+            const K3_GLOBAL unsigned long long *row = tbl + (long long)(w + NW * lane) * M * 2;
+            unsigned long long a = __hip_atomic_load(row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((unsigned)(a >> 32) != tag) {
+                const long long t0 = wall_clock64();
+                const long long lim = (long long)__hip_atomic_load(to + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                do {
+                    __builtin_amdgcn_s_sleep(1);
+                    a = __hip_atomic_load(row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if ((unsigned)(a >> 32) == tag) break;
+                    if (wall_clock64() - t0 > lim || __hip_atomic_load(to, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                        __hip_atomic_store(to, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        *s_to = 1;
+                        break;
+                    }
+                } while (true);
+            }
+        }
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(unsigned long long)tbl, 0, nr * M * 16, 0x00020000);
+        const int cntw = nrw * M;                                           // this wavefront's granules (16 bytes: {low word | tag}, {high word | tag})
+        int ge[U];                                                          // granule u of this lane, as its index in the shard's table = in the staging area
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = lane + 64 * u, ec = e < cntw ? e : cntw - 1, j = ec / M;
+            ge[u] = (w + NW * j) * M + (ec - j * M);
+        }
+        const long long t_begin = wall_clock64();
+        for (;;) {
+            int bad = 0;
+            u32x4_t xs[U];
+            ++fetches;
+#pragma unroll
+            for (int u = 0; u < U; ++u) xs[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, ge[u] * 16, 0, 16);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                bad |= (xs[u].y != tag) | (xs[u].w != tag);
+                if (lane + 64 * u < cntw) stage[ge[u]] = __hiloint2double((int)xs[u].z, (int)xs[u].x);
+            }
+            if (!__any(bad)) break;
+            // a word was not there yet: fetch again, bounded like every other wait (another wavefront's time-out ends this one too)
+            if (*(volatile K3_LDS int *)s_to) break;
+            if (lane == 0 && (wall_clock64() - t_begin > (long long)__hip_atomic_load(to + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
+                              __hip_atomic_load(to, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                __hip_atomic_store(to, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                *s_to = 1;
+            }
+            if (*(volatile K3_LDS int *)s_to) break;
+            __builtin_amdgcn_s_sleep(4);
+        }
+    }
+    __syncthreads();
+    if (*s_to) return false;
+    if (threadIdx.x == 0) {
+        // (SMCMI_PROF2: when every row of the shard was staged, and how many fetches wavefront 0 made of its own rows)
+        K3_GLOBAL long long *pw = (K3_GLOBAL long long *)hp->pw;
+        if (pw && tag == hp->ptag) { pw[2 * KIND] = wall_clock64(); pw[2 * KIND + 1] = fetches; }
+    }
+    const int t = threadIdx.x;
+    if (t < 2 * M) {                                            // (whole quads)
+        const int h = t & 3, pr = t >> 2;
+        const double ninf = -__builtin_inf();
+        double p0, p1, pm = ninf;
+        // NJ steps of 8 rows: slices 2h, 2h + 1 in ascending row order
+        auto steps = [&](auto nj_) __attribute__((always_inline)) {
+            constexpr int NJ = decltype(nj_)::value;
+            f64x2 x[NJ][2];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int r = 2 * h + q + 8 * j;
+                    x[j][q] = *reinterpret_cast<const K3_LDS f64x2 *>(stage + (r < nr ? r : nr - 1) * M + 2 * pr);
+                }
+            }
+            double a0[2] = {0.0, 0.0}, a1[2] = {0.0, 0.0}, am[2] = {ninf, ninf};
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const bool there = 2 * h + q + 8 * j < nr;
+                    a0[q] = a0[q] + (there ? x[j][q].x : 0.0);
+                    a1[q] = a1[q] + (there ? x[j][q].y : 0.0);
+                    if constexpr (MAXI >= 0) am[q] = fmax(am[q], there ? ((MAXI & 1) ? x[j][q].y : x[j][q].x) : ninf);
+                }
+            }
+            p0 = a0[0] + a0[1]; p1 = a1[0] + a1[1];
+            if constexpr (MAXI >= 0) pm = fmax(am[0], am[1]);
+        };
+        const int nj = (nr + 7) >> 3;                           // (block-uniform)
+        if (nj == 4) steps(std::integral_constant<int, 4>());
+        else if (nj == 3) steps(std::integral_constant<int, 3>());
+        else if (nj == 2) steps(std::integral_constant<int, 2>());
+        else steps(std::integral_constant<int, 1>());
+        const double q0 = fetch_xor<1>(p0), q1 = fetch_xor<1>(p1);
+        p0 = p0 + q0; p1 = p1 + q1;
+        const double r0 = fetch_xor<2>(p0), r1 = fetch_xor<2>(p1);
+        p0 = p0 + r0; p1 = p1 + r1;
+        double run0 = 0.0 + p0, run1 = 0.0 + p1;
+        if constexpr (MAXI >= 0) {
+            const double qm = fetch_xor<1>(pm);
+            pm = fmax(pm, qm);
+            const double rm = fetch_xor<2>(pm);
+            pm = fmax(pm, rm);
+            const double runm = fmax(ninf, pm);
+            if ((MAXI & 1) == 0 && 2 * pr == MAXI) run0 = runm;
+            if ((MAXI & 1) == 1 && 2 * pr + 1 == MAXI) run1 = runm;
+        }
+        if (h == 0) {
+            const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void *)(unsigned long long)dst, 0, M * 16, 0x00020000);
+            const unsigned long long b0 = (unsigned long long)__double_as_longlong(run0), b1 = (unsigned long long)__double_as_longlong(run1);
+            const u32x4_t g0 = {(unsigned)b0, tag, (unsigned)(b0 >> 32), tag}, g1 = {(unsigned)b1, tag, (unsigned)(b1 >> 32), tag};
+            __builtin_amdgcn_raw_buffer_store_b128(g0, drs, pr * 32, 0, /*sc1: agent scope, as gran_store's stores*/ 16);
+            __builtin_amdgcn_raw_buffer_store_b128(g1, drs, pr * 32 + 16, 0, 16);
+        }
+    }
     return true;
 }
 
@@ -1002,6 +1188,11 @@ __device__ inline bool k3_rides(const RunParams &rp, const Seg3Args &sa, const P
 #define K3_TOTALS_CM(tbl_, tag_) gather_totals((tbl_), g.V, MCM, -1, (tag_), sa.to, &s_to, s_tot, s_vt, sys)
 #define K3_TOTALS_MUT(tbl_, tag_, out_) gather_totals((tbl_), g.V, RMUT, RMAX_IDX, (tag_), sa.to, &s_to, s_tot, s_vt, sys, (out_))
 #endif
+// a gatherer's sweep of its shard's rows (K3H_GATHER): k3_gather, or for a shard of more than K3G_ROWS rows the unchanged gather_vshard, both out
+// of line (the dispatch stands here, block-uniform on a kernel argument: inside k3_gather the second call made it a non-leaf function that
+// saves its return address through scratch and waits for that reload - and with it for the posted stores - before it returns)
+#define K3_GATHER(M_, MAXI_, KIND_, tag_) \
+    (__builtin_expect(g.nb2 <= K3G_ROWS, 1) ? k3_gather<M_, MAXI_, KIND_>(&s_gh, (tag_)) : k3_gather_wide<M_, MAXI_, KIND_>(&s_gh, (tag_)))
 // K3H_SW: the window of the proposed schedule begin_stage(n + 1) walks depends on Post2::j of stage n alone, which is final with the stage's
 // post2 - a proposal, an MH step and a hand-over in front of that begin.  It is filled there (the workers behind their mutation row, the
 // gatherers behind their post2), so its load from the schedule runs under the hand-over instead of in front of the Newton predictor that
@@ -1101,6 +1292,16 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         s_ho.to = sa.to; s_ho.tot = (K3_LDS double *)s_tot; s_ho.vt = (K3_LDS double *)s_vt; s_ho.s_to = (K3_LDS int *)&s_to; s_ho.nvs = g.V;
     }
 #endif
+#if (K3HO) & K3H_GATHER
+    __shared__ K3Gh s_gh;                                       // (k3_gather: what a gatherer's sweeps have in common)
+    if (tid == 65 && !worker) {
+        const int vg_ = (int)blockIdx.x - W;
+        s_gh.tbl[0] = sa.g_cm + (long long)vg_ * g.nb2 * MCM * 2; s_gh.tbl[1] = sa.g_mut + (long long)vg_ * g.nb2 * RMUT * 2;
+        s_gh.dst[0] = sa.gt_cm + (long long)(g.v0 + vg_) * MCM * 2; s_gh.dst[1] = sa.gt_mut + (long long)(g.v0 + vg_) * RMUT * 2;
+        s_gh.to = sa.to; s_gh.pw = sa.gprof ? sa.gprof + PROF2_GPOLL + 4 * vg_ : nullptr; s_gh.ptag = sa.tag_base | (unsigned)sa.prof_stage;
+        s_gh.stage = (K3_LDS double *)lds_at<double, O3[lds::S_gather]>(sm); s_gh.s_to = (K3_LDS int *)&s_to; s_gh.nr = g.nb2;
+    }
+#endif
     if (tid < nf) L.fi[tid] = md->free_inds[tid];
     __syncthreads();
     const RunParams &rp = s_rp;
@@ -1186,10 +1387,14 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         bool cm_posted = false;
         auto sweep_cm = [&](int ns) __attribute__((always_inline)) -> bool {
             const unsigned tg = sa.tag_base | (unsigned)ns;
+#if (K3HO) & K3H_GATHER
+            return K3_GATHER(MCM, -1, 0, tg);
+#else
             const long long rp_ = (RIDE && (ns & 1)) ? (long long)k3_copy_words(g.Vl * g.nb2) : 0, tp_ = K3_TPAR(ns);
             return gather_vshard<T3>(sa.g_cm + rp_ + (long long)vg * g.nb2 * MCM * 2, g.nb2, MCM, -1, tg, sa.to, &s_to,
                                      [&](int idx, double val) { post_total(sa.gt_cm + tp_, sa.off_cm + tp_, ((long long)(g.v0 + vg) * MCM + idx) * 2, val, tg); }, g_stage,
                                      (sa.gprof && ns == sa.prof_stage) ? sa.gprof + PROF2_GPOLL + 4 * vg : nullptr);
+#endif
         };
         for (;; ++n) {
             const unsigned tag = sa.tag_base | (unsigned)n;
@@ -1231,9 +1436,14 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             __syncthreads();
             K3_FILL_SW(s_b[n & 1].po);
             K3_WALL(sa.gprof, PROF2_GATH + 6 * vg + 3);
+#if (K3HO) & K3H_GATHER
+            (void)rpar; (void)tpar; (void)post_total; (void)g_stage;      // (the riding and several-handle kernels' operands: K3HO is 0 there)
+            if (!K3_GATHER(RMUT, RMAX_IDX, 1, tag)) break;
+#else
             if (!gather_vshard<T3>(sa.g_mut + rpar + (long long)vg * g.nb2 * RMUT * 2, g.nb2, RMUT, RMAX_IDX, tag, sa.to, &s_to,
                                    [&](int idx, double val) { post_total(sa.gt_mut + tpar, sa.off_mut + tpar, ((long long)(g.v0 + vg) * RMUT + idx) * 2, val, tag); }, g_stage,
                                    (sa.gprof && n == sa.prof_stage) ? sa.gprof + PROF2_GPOLL + 4 * vg + 2 : nullptr)) break;
+#endif
             K3_WALL(sa.gprof, PROF2_GATH + 6 * vg + 4);
             cm_posted = false;
             if (RIDE && k3_rides(rp, sa, s_b[n & 1].po, n, sys)) { if (!sweep_cm(n + 1)) break; cm_posted = true; }
