@@ -121,6 +121,10 @@ struct DevState {
     double shift[MAXD];        // centering used by the one-pass moment kernel (previous mean)
     double mean[MAXD];         // θ_bar
     double cov[MAXD * MAXD];   // R (row-major d x d)
+    // INVARIANT (prologue.hpp k2_run_result, run2.hpp res2_state_words): a run of engines 2 / 3 writes the device copy of this struct only up
+    // to cov[d * d] - the scalars, sol, shift, mean, cov.  A single-handle run ends by copying exactly those words back into the handle's host
+    // copy; everything below keeps what the host held at the run's start.  A kernel of engines 2 / 3 that comes to write a member below this
+    // line (block layout, L, mut_*) must grow res2_state_words with it, or the host copy falls behind the device's without a word.
     int n_blocks;
     int max_db;                // largest block length
     int block_ptr[MAXD + 1];

@@ -21,6 +21,7 @@
 #include "stage2.hpp"
 #include "stage2b.hpp"
 #include "stage3.hpp"
+#include "prologue.hpp"
 
 using namespace smcmi;
 struct CallbackBuffers;            // pinned staging buffers of the host-likelihood path (callback.hpp)
@@ -50,6 +51,8 @@ struct Eng2 {
     // a segment's exit note in host-mapped memory (one handle): [0] = the launch sequence number of the segment that has left, behind it a copy of
     // Ctl2 - the host learns of a batch's end (or of a stage that must resample) without a device-to-host copy and a stream sync
     void *h_note3 = nullptr, *d_note3 = nullptr;
+    // what the end of a run leaves in host-mapped memory (prologue.hpp k2_run_result): DevState as far as the run wrote it, the segments' stage counts
+    unsigned long long *h_res = nullptr, *d_res = nullptr;
     int seg_ch = 1;                  // 512-particle chunks per segment worker (2: one handle of 126 977 .. 253 952 particles, α = 1, a cheap likelihood)
     int e3_state = 0;                // 0 untested, 1 usable (residency self-test passed), -1 off for this handle
     int seg_attr_set = 0;         /* bits 0 / 1: α = 1 / mixture variant, bits 2 / 3: their riding instantiations, bits 4 / 5: two chunks per worker */       // k3_segment's dynamic-LDS opt-in done on this handle's device
@@ -77,6 +80,11 @@ struct smcmi_handle {
     Records rec{};
     double *d_sched = nullptr;
     int sched_len = 0;
+    // host-mapped inputs the device reads itself instead of a copy in stream order: the schedule a fresh single-handle run proposes (its
+    // prologue launch copies it into d_sched), the "no finite-likelihood draw" word of the prior draw
+    double *h_sched_m = nullptr, *d_sched_m = nullptr;
+    int sched_m_len = 0;
+    int *h_flag_m = nullptr, *d_flag_m = nullptr;
     // scratch
     int nb_e = 0, nb_m = 0, nb_mr = 0, nb_mut = 0, nb_mut_ls4 = 0, mut_T = 0, nb_reg = 0, reg_T = 0;
     size_t mut_lds = 0, mom_lds = 0, reg_lds_base = 0, prep_lds = 0;
@@ -90,7 +98,7 @@ struct smcmi_handle {
     // centre of the one-pass moments at the head of a chain (kernels.hpp k_center_*): CENTER_SLOTS rows of 2 d + 1 doubles (one per shard),
     // the shift and its "apply" word (d + 1), nb_c block rows of 2 d
     double *d_center = nullptr;
-    int nb_c = 0;
+    int nb_c = 0, nb_p = 0;          // (nb_p: block rows of the prologue launch of a fresh run, prologue.hpp)
     bool center_stale = true;        // the cloud came from outside since DevState::shift was last set (create, upload, prior draw, row copies)
     std::vector<double> lik_host_data[2], lik_host_aux[2];   // host copies (lgss_kalman only): is the old vintage a prefix of the new one?
     // peer mailbox of sharded engine-2 runs (stage2.hpp Mailbox): this handle's table, the peers' tables as mapped here

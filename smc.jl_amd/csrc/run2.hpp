@@ -58,6 +58,13 @@ static int ensure_eng2(smcmi_handle *h, int world, const RunPlan &p) {
         HIP_TRY(hipMemsetAsync(e->d_gran3, 0xFF, gw * sizeof(unsigned long long), h->stream));
         HIP_TRY(hipMemsetAsync(e->d_done3, 0, SEG3_MAX_LAUNCHES * sizeof(int), h->stream));
     }
+    {
+        // (what the end of a run leaves for the host, prologue.hpp k2_run_result: host-mapped; without it the run ends with its copies)
+        unsigned long long *hp = nullptr, *dp = nullptr;
+        if (e->mem.alloc(&hp, RES2_WORDS, devmem::Kind::Mapped, &dp) == hipSuccess) memset(hp, 0, RES2_WORDS * sizeof(unsigned long long));
+        else (void)hipGetLastError();
+        e->h_res = hp; e->d_res = dp;
+    }
     HIP_TRY(hipMemsetAsync(e->d_pre, 0, sizeof(Prop2Glob), h->stream));
     HIP_TRY(hipMemsetAsync(e->d_tick, 0, 2 * V2_MAXV * TICK2_STRIDE * sizeof(int), h->stream));
     HIP_TRY(hipMemsetAsync(e->rows_mut, 0, n2 * RMUT * sizeof(double), h->stream));
@@ -148,6 +155,12 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     const bool alone = g.world == 1 && g.hs.size() == 1;            // (one handle: center_single behind its push, below)
     if (!alone) { if (int e = center_group(g, !cont)) return e; }
     // ---- per-handle set-up: run parameters and the stage-1 state in DevState (as engine 1), then imported into Ctl2
+    // One handle, a fresh run: everything between here and the first stage that used to be a copy, a fill or a launch of its own - the push of
+    // DevState with its sync, the schedule, the centre of the cloud, the first records and history columns, the import into Ctl2, cleared
+    // tickets and stage counts, engine 3's time-out words and Sel3Args - is ONE launch (prologue.hpp k2_run_prologue), enqueued below once
+    // engine 3's inputs are known.  (development, SMCMI_RUN_PROLOGUE=0: one by one as before)
+    const bool pro_ok = alone && !cont && sw().run_prologue != 0;
+    bool pro = false;
     std::vector<RunPlan> plans(g.hs.size());
     for (auto *&h : g.hs) {
         HIP_TRY(hipSetDevice(h->cfg.device));
@@ -158,18 +171,22 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         if (multi && ensure_shard_buffers(h)) return SMCMI_ERR_HIP;
         // (a fresh run rebuilds the loop state from scratch: only a continuation needs what the device holds - one 70 KB copy and a host
         // round trip less at the start of every run)
-        if ((cont && pull_state(h)) || upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
+        if (cont && pull_state(h)) return SMCMI_ERR_HIP;
+        pro = pro_ok && stage_sched(h, sched.data(), rc->n_phi);
+        if (!pro && upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
         RunParams rp = make_run_params(h, rc);
         rp.shift_lag = shift_lag ? (lag_env < 0 ? lag_env : std::max(lag_env, 1)) : 0;
         // (a continuation goes on from the largest energy the last begin saw: Begin2::e_seen stays)
-        if (int e = start_state(h, rc, rp, true)) return e;
+        if (int e = start_state(h, rc, rp, true, !pro)) return e;
         if (cont && h->h_st.stage != h0->h_st.stage) return set_err(SMCMI_ERR_STATE, "shards hold different loop states");
-        if (alone) { if (int e = center_single(h, !cont)) return e; }
-        else center_apply(h);
-        if (!cont) { if (int e = first_records(h, rc, true)) return e; }
-        // (the run's first records ride on the import kernel: four 8-byte host copies and a stream sync less per run)
-        k2_state<<<1, 64, 0, h->stream>>>(h->d_st, h->e2->d_ctl, 1, h->rec, cont ? 0 : 1, initial_ess(h, rc), rc->c, rc->target);
-        HIP_TRY(hipMemsetAsync(h->e2->d_tick, 0, 2 * V2_MAXV * TICK2_STRIDE * sizeof(int), h->stream));
+        if (!pro) {
+            if (alone) { if (int e = center_single(h, !cont)) return e; }
+            else center_apply(h);
+            if (!cont) { if (int e = first_records(h, rc, true)) return e; }
+            // (the run's first records ride on the import kernel: four 8-byte host copies and a stream sync less per run)
+            k2_state<<<1, 64, 0, h->stream>>>(h->d_st, h->e2->d_ctl, 1, h->rec, cont ? 0 : 1, initial_ess(h, rc), rc->c, rc->target);
+            HIP_TRY(hipMemsetAsync(h->e2->d_tick, 0, 2 * V2_MAXV * TICK2_STRIDE * sizeof(int), h->stream));
+        }
         // random numbers drawn ahead: while K1 leaves most CUs idle (small clouds = the direct geometry with 512-thread mutation blocks)
         Eng2 *e = h->e2;
         e->rng_ahead = false; e->z_ahead = 0; e->n_steps = rc->n_mh_steps; e->n_blocks = rc->n_blocks;
@@ -279,13 +296,16 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     auto mut_rows = [&](smcmi_handle *h) { return mb_live[1] ? mb_rows(h, 1, h->e2->vt_mut, RMUT) : view(h, h->e2->rows_mut, h->e2->vt_mut, g0.nb2, RMUT); };
     auto cm_rows = [&](smcmi_handle *h) { return mb_live[0] ? mb_rows(h, 0, h->e2->vt_cm, npf) : view(h, h->e2->rows_cm, h->e2->vt_cm, g0.nb1, npf); };
     auto gm_rows = [&](smcmi_handle *h) { return view(h, h->e2->rows_gm, h->e2->vt_gm, g0.nbg, np); };
-    // energy maximum of the initial cloud in the mutation-row layout (stage 2's energy shift)
-    for (auto *h : g.hs) {
-        HIP_TRY(hipSetDevice(h->cfg.device));
-        k_energy_max<<<g0.Vl * g0.nb2, TB, 0, h->stream>>>(h->cl, h->d_st, h->e2->rows_mut + RMAX_IDX, RMUT, 0);   // (a maximum: the blocks need not be the rows' particles)
-    }
-    // (mutation rows of 256-thread blocks are paired: the canonical row stands for 512 particles, whatever the block size)
-    if (int e = publish(&Eng2::rows_mut, &Eng2::vt_mut, g0.nb2, RMUT, RMAX_IDX, 0)) return e;
+    // energy maximum of the initial cloud in the mutation-row layout (stage 2's energy shift); behind the launch that leaves DevState
+    auto enq_energy_max = [&]() -> int {
+        for (auto *h : g.hs) {
+            HIP_TRY(hipSetDevice(h->cfg.device));
+            k_energy_max<<<g0.Vl * g0.nb2, TB, 0, h->stream>>>(h->cl, h->d_st, h->e2->rows_mut + RMAX_IDX, RMUT, 0);   // (a maximum: the blocks need not be the rows' particles)
+        }
+        // (mutation rows of 256-thread blocks are paired: the canonical row stands for 512 particles, whatever the block size)
+        return publish(&Eng2::rows_mut, &Eng2::vt_mut, g0.nb2, RMUT, RMAX_IDX, 0);
+    };
+    if (!pro) { if (int e = enq_energy_max()) return e; }
 
     // ---- engine 3: runs of stages that neither resample nor need a certificate pass become one persistent launch each
     bool e3 = false;
@@ -347,7 +367,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             // (tags restart with every run of sharded segments: the tables the peers post into start cleared, like the segments' own below)
             HIP_TRY(hipMemsetAsync(h0->d_mbox + MB_SEL_OFF, 0xFF, sizeof(unsigned long long) * MB_SEL_TABLE_WORDS, h0->stream));
         }
-        HIP_TRY(hipMemcpyAsync(e->d_sel3, &sl, sizeof(sl), hipMemcpyHostToDevice, h0->stream));
+        if (!pro) HIP_TRY(hipMemcpyAsync(e->d_sel3, &sl, sizeof(sl), hipMemcpyHostToDevice, h0->stream));       // (else: an argument of the prologue launch)
       }
     // (the note outlives a run and sequence numbers start over - sharded segments reset them, 65 535 launches wrap them: a note left by an
     // earlier run must never equal the number a launch of this run is waited for under.  Every run ends with its stream drained, so nothing
@@ -358,10 +378,10 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     int last_note_seq = -1;      // sequence number of the latest segment launch that leaves a note; -1: the stream's last launch is not such a segment
     struct SegRange { int a, b; bool enter; };
     std::vector<SegRange> seg_ranges;              // stages each segment launch was enqueued for (error diagnosis)
+    // (across ranks the first hand-over of a segment also absorbs the skew between the ranks' hosts: a longer bound)
+    const double to_ms = sw().seg_timeout_ms > 0.0 ? sw().seg_timeout_ms : (seg_sys ? 1000.0 : 200.0);
     if (e3) {
-        // (across ranks the first hand-over of a segment also absorbs the skew between the ranks' hosts: a longer bound)
-        const double to_ms = sw().seg_timeout_ms > 0.0 ? sw().seg_timeout_ms : (seg_sys ? 1000.0 : 200.0);
-        for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); if (int e = seg3_time_out_words(h, to_ms)) return e; }
+        if (!pro) for (auto *h : g.hs) { HIP_TRY(hipSetDevice(h->cfg.device)); if (int e = seg3_time_out_words(h, to_ms)) return e; }
         if (seg_sys) {
             // one launch sequence for all handles - the tags (sequence << 16 | stage) must agree - restarted for every run on cleared tables:
             // this handle's rows, and the totals tables every handle posts into
@@ -375,6 +395,27 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             }
             if (int e = g.barrier()) return e;           // nobody posts before every table is cleared
         }
+    }
+    if (pro) {
+        smcmi_handle *h = h0;
+        Eng2 *e = h->e2;
+        Pro2Args a{};
+        a.st = h->d_st; a.ctl = e->d_ctl; a.rec = h->rec;
+        memcpy(&a.head, &h->h_st, ST_HEAD_BYTES);                    // (start_state: everything behind these bytes is zero)
+        a.ess0 = initial_ess(h, rc); a.c0 = rc->c; a.acc0 = rc->target;
+        a.max_stages = h->cfg.max_stages; a.n = h->n;
+        if (h->cfg.store_history) { a.hist_w = h->d_hist_w; a.hist_W = h->d_hist_W; a.W0 = h->cl.buf[h->h_st.cur] + (long long)(h->R - 1) * h->n; }
+        a.tick = e->d_tick; a.n_tick = 2 * V2_MAXV * TICK2_STRIDE;
+        a.done3 = e->d_done3; a.n_done3 = SEG3_MAX_LAUNCHES;
+        if (e3) { a.to3 = e->d_to3; a.to3_bound = (unsigned long long)(to_ms * 1e5); }          // 100 MHz wall clock (seg3_time_out_words)
+        if (sel_inside) { a.sel3_dst = e->d_sel3; a.sel3 = e->h_sel3; }
+        a.sched = h->d_sched; a.sched_src = h->d_sched_m; a.n_phi = rc->n_phi;
+        a.cloud = h->cl.buf[h->h_st.cur]; a.d = h->d; a.R = h->R; a.part = center_out(h) + h->d + 1; a.ticket = center_ticket(h);
+        a.center = center_on() ? 1 : 0;
+        k2_run_prologue<<<h->nb_p, TB, 0, h->stream>>>(a);
+        HIP_TRY(hipGetLastError());
+        h->center_stale = false;
+        if (int e2 = enq_energy_max()) return e2;
     }
     const bool profile = rc->use_graph == 2;
     MutationEvents evs(profile);                 // tagged with the stage of the launch
@@ -584,7 +625,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (profile && sa.done_out) { HIP_TRY(evs3.event(&e0)); HIP_TRY(evs3.event(&e1)); hipEventRecord(e0, h->stream); }       // (pair k belongs to launch k)
         // (the stage counters of all launches of a run are cleared once, in front of its first segment: a fill per launch was 5 µs each)
-        if (sa.done_out && seg_launches == 0) HIP_TRY(hipMemsetAsync(e->d_done3, 0, SEG3_MAX_LAUNCHES * sizeof(int), h->stream));
+        if (sa.done_out && seg_launches == 0 && !pro) HIP_TRY(hipMemsetAsync(e->d_done3, 0, SEG3_MAX_LAUNCHES * sizeof(int), h->stream));      // (pro: the prologue launch has)
 #define SMCMI_CALL(D) if (int lrc = launch_k3_segment<D>(h, ma, sa, rc->n_blocks, rc->alpha == 1.0, shift_lag)) return lrc
         SMCMI_D_SWITCH(d, SMCMI_CALL)
 #undef SMCMI_CALL
@@ -711,6 +752,20 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     Ctl2 c{};
     const auto t0 = std::chrono::steady_clock::now();
     bool finished = false;
+    // One handle: the launch that exports Ctl2 into DevState also leaves DevState - as far as a run of engines 2 / 3 writes it; the rest is what
+    // the handle holds since the run's start - and the segments' stage counts in host-mapped memory (prologue.hpp k2_run_result): ONE sync at
+    // the end of the run, no copy behind it.  A batch that runs to `room` enqueues it right behind its segment - the run is expected to end
+    // there, and the launch then waits for nobody's reaction to the exit note; whatever is enqueued behind it voids it (an export in mid-run
+    // touches nothing a stage reads: stages read RunParams and the solver copies of DevState).
+    const bool res_on = alone && sw().run_prologue != 0 && h0->e2->h_res != nullptr && h0->d <= 16;
+    bool res_queued = false;                     // the stream's last launch is k2_run_result
+    auto enq_result = [&]() -> int {
+        const int nd = h0->e2->d_done3 ? std::min(seg_launches, RES2_DONE_MAX) : 0;
+        k2_run_result<<<1, 64, 0, h0->stream>>>(h0->d_st, h0->e2->d_ctl, h0->e2->d_res, res2_state_words(h0->d), h0->e2->d_done3, nd);
+        HIP_TRY(hipGetLastError());
+        res_queued = true;
+        return 0;
+    };
     // one handle, predictions on, selection in place: behind the two certificate stages every stage of the run belongs to ONE segment, which
     // leaves by itself at ϕ = 1, at a stall or at capacity - nothing enqueued behind it is wasted, so the batch runs to `room` instead of
     // cutting the segment in two at a host sync (a write-back, a reload and a prologue of the cloud around ~50 µs of idle GPU).  A batch that
@@ -718,6 +773,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     const bool whole_run_batches = adaptive && e3 && sel_inside && predict_select && sel_mode == 0 && rc->sync_every <= 0 && g.hs.size() == 1 && !seg_sys;
     bool last_stalled = false;
     while (!finished) {
+        res_queued = false;
         const int room = max_iter - launched;
         const bool to_room = whole_run_batches && book.spec_on && !last_stalled && force_sel < 0;
         const int batch = adaptive && !to_room ? left.batch(book.spec_on || !spec_ok ? cur_sync : std::min(cur_sync, cert_sync), room) : room;
@@ -766,6 +822,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
             ++launched;
         }
         if (int e = flush_seg()) return e;
+        if (res_on && to_room && last_note_seq >= 0) { if (int e = enq_result()) return e; }
         if (int e = read_ctl(&c)) return e;
         if (sw().trace) {                       // development only
             const Post2 &tp = c.ps[0].stage >= c.ps[1].stage ? c.ps[0] : c.ps[1];
@@ -775,6 +832,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         while (c.status.code == 2 || c.status.code == 3 || c.status.code == 4 || c.status.code == 6) {
             const int sn = c.status.stage, code = c.status.code;
             stalled = true;
+            res_queued = false;
             // mailbox: a resumed stage posts under fresh tags into tables a slower handle may still be polling for the stalled
             // stage's - every handle must have left the stalled batch first
             if (mbox) { if (int e = g.barrier()) return e; mb_rewind(sn, code == 3); }
@@ -845,6 +903,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         if (p.phi_n >= 1.0 || launched >= max_iter) {
             // the last enqueued stage reached ϕ = 1 (or the capacity is used up): the next stage's begin folds the last acceptance
             // rate and closes the run
+            res_queued = false;
             if (int e = enq_begin(p.stage + 1)) return e;
             if (int e = read_ctl(&c)) return e;
             finished = true;
@@ -858,13 +917,22 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
     }
     // (a batch that ended with a segment's exit note was read before the launch had finished: everything behind this line reads what it left)
     HIP_TRY(hipSetDevice(h0->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h0->stream));
-    if (h0->e2->d_prof) { if (int e = prof2_report(h0, g0, seg_launches)) return e; }
-    for (auto *h : g.hs) {
-        HIP_TRY(hipSetDevice(h->cfg.device));
-        k2_state<<<1, 64, 0, h->stream>>>(h->d_st, h->e2->d_ctl, 0);
-        if (pull_state(h)) return SMCMI_ERR_HIP;
-        h->last_n_stages = h->h_st.stage;
+    if (res_on) {
+        if (!res_queued) { if (int e = enq_result()) return e; }
+        HIP_TRY(hipStreamSynchronize(h0->stream));
+        memcpy(&h0->h_st, h0->e2->h_res, sizeof(unsigned long long) * (size_t)res2_state_words(h0->d));
+        h0->h_st.e_shift = 0.0;                 // (as pull_state: the shift belongs to a running stage chain)
+        h0->last_n_stages = h0->h_st.stage;
+        if (h0->e2->d_prof) { if (int e = prof2_report(h0, g0, seg_launches)) return e; }
+    } else {
+        HIP_TRY(hipStreamSynchronize(h0->stream));
+        if (h0->e2->d_prof) { if (int e = prof2_report(h0, g0, seg_launches)) return e; }
+        for (auto *h : g.hs) {
+            HIP_TRY(hipSetDevice(h->cfg.device));
+            k2_state<<<1, 64, 0, h->stream>>>(h->d_st, h->e2->d_ctl, 0);
+            if (pull_state(h)) return SMCMI_ERR_HIP;
+            h->last_n_stages = h->h_st.stage;
+        }
     }
     const auto t1 = std::chrono::steady_clock::now();
     const DevState &s = h0->h_st;
@@ -878,7 +946,8 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         const int nl = std::min(seg_launches, SEG3_MAX_LAUNCHES);
         std::vector<int> done(nl);
         HIP_TRY(hipSetDevice(h0->cfg.device));
-        HIP_TRY(hipMemcpy(done.data(), h0->e2->d_done3, sizeof(int) * nl, hipMemcpyDeviceToHost));
+        if (res_on && nl <= RES2_DONE_MAX) memcpy(done.data(), h0->e2->h_res + RES2_STATE_WORDS, sizeof(int) * nl);
+        else HIP_TRY(hipMemcpy(done.data(), h0->e2->d_done3, sizeof(int) * nl, hipMemcpyDeviceToHost));
         for (int k = 0; k < nl; ++k) res->segment_stages += done[k];
         int timed_stages = 0;
         for (size_t k = 0; k + 1 < evs3.events.size(); k += 2) {

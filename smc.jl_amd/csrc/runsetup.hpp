@@ -42,7 +42,8 @@ static double initial_ess(const smcmi_handle *h, const smcmi_run_config *rc) { r
 // loop scalars, records and history the handle holds (left by a paused run, or put there by smcmi_set_loop_state / _set_stage_records /
 // _set_history); the caller has pulled them.  keep_e_seen: engines 2 / 3 go on from the largest energy their last begin saw (stage2.hpp
 // Begin2::e_seen); the other drivers keep none, and a later continuation on engines 2 / 3 takes the cloud's own maximum.
-static int start_state(smcmi_handle *h, const smcmi_run_config *rc, const RunParams &rp, bool keep_e_seen) {
+// push = false: the state stays in the handle - the caller's prologue launch puts it on the device (run2.hpp run_prologue: a fresh run).
+static int start_state(smcmi_handle *h, const smcmi_run_config *rc, const RunParams &rp, bool keep_e_seen, bool push = true) {
     DevState &s = h->h_st;
     if (rc->continue_run) {
         if (s.stage < 1 || s.stage >= h->cfg.max_stages) return set_err(SMCMI_ERR_STATE, "no loop state to continue from");
@@ -58,7 +59,7 @@ static int start_state(smcmi_handle *h, const smcmi_run_config *rc, const RunPar
         s.c = rc->c; s.accept = rc->target;                     // initialize_cloud_settings!, initialization.jl:196-211
         s.ess_prev = initial_ess(h, rc);
     }
-    return push_state(h);
+    return push ? push_state(h) : 0;
 }
 // A fresh run's stage-1 records, resample flags and history columns (w[:,1] = 0, W[:,1] = weights; smc_main.jl:363-366).  on_import:
 // run2_impl's variant - the four records ride on its import kernel (k2_state) and the column is copied by a kernel: no host copies, no

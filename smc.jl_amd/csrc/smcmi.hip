@@ -53,6 +53,9 @@ static int forget_e_seen(smcmi_handle *h) {
 static bool center_on() { return sw().center != 0; }
 static inline double *center_rows(smcmi_handle *h) { return h->d_center; }
 static inline double *center_out(smcmi_handle *h) { return h->d_center + (size_t)CENTER_SLOTS * (2 * h->d + 1); }
+static const int CENTER_TICKETS = (1 + PRO2_GROUPS + 1) / 2;      // doubles: k_center_one's one ticket word, k2_run_prologue's 1 + PRO2_GROUPS
+// (behind the block rows of whichever launch writes more of them: k_center_one's nb_c, k2_run_prologue's nb_p)
+static inline int *center_ticket(smcmi_handle *h) { return reinterpret_cast<int *>(center_out(h) + h->d + 1 + (size_t)2 * h->d * std::max(h->nb_c, h->nb_p)); }
 static int center_probe(smcmi_handle *h, int rank, int world) {
     const int d = h->d, ld = 2 * d + 1;
     if (rank < 0 || rank >= world || world > CENTER_SLOTS) return set_err(SMCMI_ERR_ARG, "too many shards");
@@ -76,7 +79,7 @@ static void center_apply(smcmi_handle *h) {
 static int center_single(smcmi_handle *h, bool fresh) {
     if ((!fresh && !h->center_stale) || !center_on()) return 0;
     double *part = center_out(h) + h->d + 1;
-    k_center_one<<<h->nb_c, TB, 0, h->stream>>>(h->cl.buf[h->h_st.cur], h->n, h->d, h->R, part, reinterpret_cast<int *>(part + (size_t)2 * h->d * h->nb_c), h->d_st);
+    k_center_one<<<h->nb_c, TB, 0, h->stream>>>(h->cl.buf[h->h_st.cur], h->n, h->d, h->R, part, center_ticket(h), h->d_st);
     h->center_stale = false;
     return 0;
 }
@@ -219,6 +222,8 @@ static int create_impl(smcmi_handle *h, const smcmi_config *cfg) {
     h->nb_e = (int)std::min<long long>(512, std::max<long long>(1, (n + 511) / 512));      // (512 rows, not 1024: less for the prepare launch to total - measured 2-4 % per run from 4e5 to 1e7 particles)
     h->nb_m = (int)std::min<long long>(256, std::max<long long>(1, (n + MT - 1) / MT));
     h->nb_c = (int)std::min<long long>(256, std::max<long long>(1, (n + 1023) / 1024));
+    // (the prologue launch of a fresh run, prologue.hpp: one particle per thread and column up to 131 072 particles - its scan is a chain of memory round trips)
+    h->nb_p = (int)std::min<long long>(512, std::max<long long>(1, (n + TB - 1) / TB));
     h->nb_mr = (int)std::min<long long>(512, std::max<long long>(std::min<long long>(64, (n + TB - 1) / TB), n / 1024));
     // mutation block size: largest of 256/128/64 threads whose per-thread LDS vectors fit 64 KiB
     for (int T : {256, 128, 64}) {
@@ -240,11 +245,11 @@ static int create_impl(smcmi_handle *h, const smcmi_config *cfg) {
         dmalloc(h->mem, &h->d_chunk_off, h->nb_e) || dmalloc(h->mem, &h->d_cum, n) || dmalloc(h->mem, &h->d_anc, n) ||
         dmalloc(h->mem, &h->d_part_mom, (size_t)std::max(h->nb_m, h->nb_mr) * h->npairs) || dmalloc(h->mem, &h->d_totals, h->npairs) ||
         dmalloc(h->mem, &h->d_acc_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(h->mem, &h->d_esum_part, (size_t)std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4}) * ES) || dmalloc(h->mem, &h->d_esum_red, (size_t)ESUM_RED_ROWS * (ES + 1)) || dmalloc(h->mem, &h->d_emax_part, std::max({h->nb_mut, h->nb_reg, h->nb_mut_ls4})) || dmalloc(h->mem, &h->d_comm, h->comm_cap) || dmalloc(h->mem, &h->d_offsets, n) ||
-        dmalloc(h->mem, &h->d_center, (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * h->nb_c + 1)) ||
+        dmalloc(h->mem, &h->d_center, (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * std::max(h->nb_c, h->nb_p) + CENTER_TICKETS)) ||
         dmalloc(h->mem, &h->d_flag, 4) || dmalloc(h->mem, &h->d_mix, (size_t)10 * (3 * 100 + 22)) || dmalloc(h->mem, &h->d_mixpos, 100))
         return SMCMI_ERR_HIP;
     h->d_prep_tick = reinterpret_cast<int *>(h->d_prep_rows + (size_t)PREP_G * PT);
-    HIP_TRY(hipMemset(h->d_center + (size_t)(CENTER_SLOTS * (2 * h->d + 1) + h->d + 1 + 2 * h->d * h->nb_c), 0, sizeof(double)));      // k_center_one's ticket
+    HIP_TRY(hipMemset(center_ticket(h), 0, CENTER_TICKETS * sizeof(double)));      // k_center_one's ticket (and k2_run_prologue's)
     HIP_TRY(hipMemset(h->d_prep_tick, 0, 8 * sizeof(double)));
     if (h->cfg.store_history) {
         if (dmalloc(h->mem, &h->d_hist_w, (size_t)n * ms) || dmalloc(h->mem, &h->d_hist_W, (size_t)n * ms)) return SMCMI_ERR_HIP;
@@ -437,11 +442,21 @@ extern "C" int smcmi_init_from_prior(smcmi_handle *h) {
     h->center_stale = true;
     if (closure_lik(h)) return callback_init_from_prior(h);           // user likelihood: device draws, the callback scores
     if (h->d > 64) return set_err(SMCMI_ERR_UNSUPPORTED, "device prior sampling: the RNG tags carry the parameter index in 6 bits");
-    HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
-    k_init_prior<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_model, h->cfg.seed, h->cfg.gid0, h->d_flag);
+    // the "no finite-likelihood draw" word lives in host-mapped memory: the host clears it (no draw is in flight: each one is waited for
+    // below), a thread that gives up sets it, the one sync shows it - no fill in front of the launch, no copy behind it
+    if (!h->h_flag_m && h->mem.alloc(&h->h_flag_m, 16, devmem::Kind::Mapped, &h->d_flag_m) != hipSuccess) (void)hipGetLastError();
     int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, h->d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->h_flag_m) {
+        *(volatile int *)h->h_flag_m = 0;
+        k_init_prior<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_model, h->cfg.seed, h->cfg.gid0, h->d_flag_m);
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        flag = *(volatile int *)h->h_flag_m;
+    } else {
+        HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
+        k_init_prior<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_model, h->cfg.seed, h->cfg.gid0, h->d_flag);
+        HIP_TRY(hipMemcpyAsync(&flag, h->d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
     if (flag) return set_err(SMCMI_ERR_STATE, "initial draw: no finite-likelihood draw found");
     return 0;
 }
@@ -511,6 +526,20 @@ static int upload_sched(smcmi_handle *h, const double *sched, int n_phi) {
     HIP_TRY(h->mem.regrow(&h->d_sched, &h->sched_len, (size_t)n_phi));
     HIP_TRY(hipMemcpyAsync(h->d_sched, sched, sizeof(double) * n_phi, hipMemcpyHostToDevice, h->stream));
     return 0;
+}
+
+// the same schedule left in host-mapped memory, for a launch to copy into d_sched (run2.hpp run_prologue); false: no such memory to be had.
+// (every run ends with its stream drained: nothing still reads the words a later run overwrites)
+static bool stage_sched(smcmi_handle *h, const double *sched, int n_phi) {
+    if (h->mem.regrow(&h->d_sched, &h->sched_len, (size_t)n_phi) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (h->sched_m_len < n_phi) {
+        h->mem.release(&h->h_sched_m);
+        h->d_sched_m = nullptr; h->sched_m_len = 0;
+        if (h->mem.alloc(&h->h_sched_m, (size_t)n_phi, devmem::Kind::Mapped, &h->d_sched_m) != hipSuccess) { (void)hipGetLastError(); return false; }
+        h->sched_m_len = n_phi;
+    }
+    memcpy(h->h_sched_m, sched, sizeof(double) * (size_t)n_phi);
+    return true;
 }
 
 static const int DEFAULT_SOLVER_PASSES = 1;   // with the energy-sum predictor 1-2 passes certify the root; a stage that needs more stalls and is resumed (smcmi_run)

@@ -511,23 +511,31 @@ __device__ inline void k2_export_state(DevState *st, const Ctl2 *ctl) {
 }
 // to_ctl: DevState -> Ctl2 (a run starts); else Ctl2 -> DevState (it ends).  One kernel: the two directions are never needed in one launch
 #ifndef SMCMI_INST_UNIT
-static __global__ void k2_state(DevState *st, Ctl2 *ctl, int to_ctl, Records rec = Records{}, int fresh = 0, double ess0 = 0.0, double c0 = 0.0, double acc0 = 0.0) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (!to_ctl) { k2_export_state(st, ctl); return; }
+// DevState -> Ctl2, by one thread; fresh: the run's stage-1 records ride along.  Of *st only what stands in front of DevState::sol is read
+// (the run prologue, prologue.hpp, hands over a copy of just that), the shift comes separately.
+__device__ inline void k2_import_state(const DevState *st, const double *shift, Ctl2 *ctl, const Records &rec, int fresh, double ess0, double c0, double acc0) {
     if (fresh) { rec.phi[0] = 0.0; rec.ess[0] = ess0; rec.c[0] = c0; rec.accept[0] = acc0; }
-    Ctl2 c;
-    memset(&c, 0, sizeof(c));
+    // (written in place, word by word: a local Ctl2 indexed by the stage's parity lives in scratch, which every wavefront of the launch -
+    // the run prologue's hundreds of blocks, prologue.hpp - would be given.  The single-thread k2_state launch below, which continued and
+    // several-handle runs still take, stores the same words this way too: the same values, one store per field instead of one struct copy)
+    Ctl2 &c = *ctl;
+    static_assert(sizeof(Ctl2) % 8 == 0, "cleared as 8-byte words");
+    for (int k = 0; k < (int)(sizeof(Ctl2) / 8); ++k) reinterpret_cast<unsigned long long *>(ctl)[k] = 0ull;
     Post2 &p = c.ps[st->stage & 1];
     p.stage = st->stage; p.j = st->j; p.resampled_last = st->resampled_last; p.do_resample = 0; p.resamples = st->resamples;
     p.fold_valid = 0;                                  // no mutation rows of this chain exist yet (fresh or continued run)
     p.phi_n = st->phi_n; p.phi_prop = st->phi_prop; p.ess = st->ess_prev; p.sumw = st->sumw; p.sumw2 = st->sumw2;
     p.logz = st->logz; p.c = st->c; p.accept = st->accept; p.e_center = st->e_center; p.e_shift = 0.0;
     p.e_seen = st->e_seen;                             // (NaN on a fresh run; what the export left when a paused run goes on)
-    for (int a = 0; a < (int)(sizeof(p.shift) / sizeof(double)); ++a) p.shift[a] = st->shift[a];
+    for (int a = 0; a < (int)(sizeof(p.shift) / sizeof(double)); ++a) p.shift[a] = shift[a];
     c.ps[(st->stage & 1) ^ 1].stage = -1;
     c.bg.stage = -1;
     c.status.solver_passes = st->solver_passes;
-    *ctl = c;
+}
+static __global__ void k2_state(DevState *st, Ctl2 *ctl, int to_ctl, Records rec = Records{}, int fresh = 0, double ess0 = 0.0, double c0 = 0.0, double acc0 = 0.0) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (!to_ctl) { k2_export_state(st, ctl); return; }
+    k2_import_state(st, st->shift, ctl, rec, fresh, ess0, c0, acc0);
 }
 #endif
 
