@@ -325,6 +325,31 @@ int smcmi_mailbox_import(smcmi_handle *h, int32_t rank, int32_t world, const uin
 int smcmi_mailbox_selftest(smcmi_handle *h, int32_t rank, int32_t world, int32_t rounds, int32_t *errors_out);
 int smcmi_mailbox_active(smcmi_handle *h, int32_t *active_out);   /* 1: the last sharded run handed its per-stage sums over through the mailbox */
 int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, smcmi_result *res);
+/* ---- an ensemble of small runs in ONE launch (csrc/runens.hpp, csrc/enskernel.hpp) ----------------------------------------------
+   The reference's workloads are small (n_parts defaults to 5 000, its examples use 1 000) and are run many times over: seeds, data
+   vintages, model variants.  smcmi_run_ensemble runs n such runs at once, ONE WORKGROUP PER RUN: member k runs the whole loop of
+   src/smc_main.jl:377-508 under `rc` from its own cloud with its own seed, on the library's Philox contract, until phi = 1.  Members
+   never communicate and no workgroup waits for another; more members than the chip has CUs simply queue.
+   A member is an ordinary whole-cloud handle (n_local == n_parts, gid0 == 0) of this process, prepared exactly as for smcmi_run
+   (parameters and likelihood set, cloud uploaded or drawn with its log-likelihoods filled).  Members share the device, n_para (<= 10),
+   n_parts (<= SMCMI_ENS_MAX_PARTS: a workgroup keeps two particle-length FP64 arrays in LDS, the stage's energies and the weights a
+   selection accumulates - 128 KiB of a CU's 160 KiB at 8 192 particles), max_stages and store_history; they may differ in their seed,
+   their model (priors, bounds, fixed flags) and their device likelihood family with its parameters and data.
+   After the call handle k is in the state smcmi_run(hs[k], rc, &res[k]) would have left it in - the cloud in the current buffer, the
+   loop scalars on the device and in the host copy, the per-stage records, the w / W history (store_history), the last stage's moments -
+   and every later call works as after a solo run.  The numbers are those of the solo run up to summation order (one workgroup's trees,
+   the adaptive root certified to phi_rtol as smcmi_run_config defines it; no stage is predicted); a member's results do not depend on
+   its position or its company, and two identical calls give the same bits.  res[k].seconds is the wall time of the whole call.
+   Returns 0 when every member reached phi = 1.  A call that is refused as a whole returns the refusal's code, nothing ran and no handle
+   changed: n < 1, a NULL or repeated handle, members that differ in a shared shape -> SMCMI_ERR_ARG; a shard, a host or device
+   likelihood callback, an old-data likelihood or tempered_update_prior_weight != 0, stop_after_stage or continue_run, n_para > 10,
+   n_parts > SMCMI_ENS_MAX_PARTS, and MIXTURE PROPOSALS (alpha < 1: refused, not served) -> SMCMI_ERR_UNSUPPORTED.  Otherwise the code
+   of the lowest-indexed member that failed; status[k] (may be NULL) holds every member's own code - 0, SMCMI_ERR_NAN_ESS, _POSDEF,
+   _CAPACITY, _BRACKET - and a failing member does not disturb the others. */
+#define SMCMI_ENS_MAX_PARTS 8192
+int smcmi_run_ensemble(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, smcmi_result *res /* n entries */,
+                       int32_t *status /* n entries, may be NULL */);
+
 /* parity aid: compute_proposal_densities(para_draw, para_subset, d_subset = MvNormal(mu, Sigma), c, alpha) (src/helpers.jl:128-164;
    quirk Q1: the diagonal component's density uses the unscaled Σ_ii) evaluated by the dense mixture code of the alpha < 1 mutation
    kernels on the current device, for one block of d <= 16 entries; Sigma row-major d x d.  q0 / q1 as the reference returns them. */

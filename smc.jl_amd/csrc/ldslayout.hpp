@@ -200,6 +200,35 @@ constexpr Seg3Layout seg3(int D, int cols) {
     return l;
 }
 
+// kens_run (enskernel.hpp), one workgroup = one whole run of `n` particles: the mutation body's arrays | every block's expanded factor |
+// two particle-length arrays - the particles' energies (loglh - old_loglh), and their weights, which a selection turns into the cumulative
+// weights it searches - | the scratch of the block reductions, the moments and the proposal
+enum EnsId {
+    X_body,                               // mut2(D, 4, LIK_LDS_CAP, false): what MutBodyLds::place_body<4, LIK_LDS_CAP> carves
+    X_Ls,                                 // [D][D*D] the blocks' factors as expand_alpha1_factor leaves them (at most D blocks)
+    X_en, X_wv,                           // [n] each
+    X_red,                                // [4 * 64] block_reduce_many's wave rows
+    X_tot,                                // [64] the totals a reduction leaves for every thread
+    X_covl, X_sigf, X_A,                  // [D*D] each: covariance, its free symmetrised part, a block's scaled matrix
+    X_mean, X_muf,                        // [D] each
+    X_bfree, X_fi, X_fij,                 // [D] ints each
+    X_N
+};
+constexpr Layout<X_N> ens(int D, long long n) {
+    const size_t d = (size_t)D;
+    Layout<X_N> l;
+    l.put(X_body, mut2(D, 4, LIK_LDS_CAP, false).bytes, 1, 16);
+    l.put(X_Ls, d * d * d, D8, 16);
+    for (int id : {X_en, X_wv}) l.put(id, (size_t)n, D8);
+    l.put(X_red, 4 * 64, D8);
+    l.put(X_tot, 64, D8);
+    for (int id : {X_covl, X_sigf, X_A}) l.put(id, d * d, D8);
+    for (int id : {X_mean, X_muf}) l.put(id, d, D8);
+    for (int id : {X_bfree, X_fi, X_fij}) l.put(id, d, I4);
+    l.close();
+    return l;
+}
+
 }  // namespace lds
 
 // columns of LDS a segment kernel gets for the particle in transit (0: the particle is parked in device memory instead, Sel3Args::transit).

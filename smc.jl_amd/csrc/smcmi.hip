@@ -1322,6 +1322,10 @@ extern "C" int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_con
     return run_sharded_impl(g, rc, res);
 }
 
+#include "runens.hpp"
+extern "C" int smcmi_run_ensemble(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, smcmi_result *res, int32_t *status) {
+    return run_ensemble_impl(hs, n, rc, res, status);
+}
 
 // compute_proposal_densities (src/helpers.jl:128-164) of one move through the device's dense mixture form (kernels.hpp mix_densities):
 // the reference's own fixture (test/helpers.jl:101-127) reaches the HIP code the alpha < 1 mutation kernels run

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("SMCMI_LIBRARY") or os.path.join(os.path.dirname(_HERE
 MAX_PARA = 64
 MAX_CAND = 16
 MAX_QUANT = 16
+ENS_MAX_PARTS = 8192      # SMCMI_ENS_MAX_PARTS: particles of an ensemble member
+ENS_MAX_PARA = 10
 BEST = {"loglh": 0, "logpost": 1}
 
 PRIOR = {"normal": 0, "uniform": 1, "gamma": 2, "beta": 3, "invgamma": 4, "rootinvgamma": 5}
@@ -144,6 +146,7 @@ SYMBOLS = [
     ("smcmi_mailbox_selftest", C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("smcmi_mailbox_active", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("smcmi_run_group", C.c_int, [C.POINTER(_H), C.c_int32, C.POINTER(RunConfig), C.POINTER(Result)]),
+    ("smcmi_run_ensemble", C.c_int, [C.POINTER(_H), C.c_int32, C.POINTER(RunConfig), C.POINTER(Result), ip]),      # res, status: n entries each
     ("smcmi_weighted_quantiles", C.c_int, [_H, ip, C.c_int32, dp, C.c_int32, dp]),
     ("smcmi_weighted_quantiles_group", C.c_int, [C.POINTER(_H), C.c_int32, ip, C.c_int32, dp, C.c_int32, dp]),
     ("smcmi_best_particle", C.c_int, [_H, C.c_int32, lp, dp, dp]),

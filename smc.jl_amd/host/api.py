@@ -514,6 +514,73 @@ def smc(loglikelihood, parameters, data, *, verbose="low", n_parts=5000, n_block
     return cloud, w, W
 
 
+def smc_ensemble(loglikelihood, parameters, data, seeds, *, n_parts=5000, n_blocks=1, n_mh_steps=1, lam=2.1, n_phi=300,
+                 resampling_method="systematic", threshold_ratio=0.5, c=0.5, alpha=1.0, target=0.25, use_fixed_schedule=True,
+                 tempering_target=0.97, device=0, max_stages=None, regime_switching=False, verbose="none"):
+    """The same estimation over many seeds in ONE launch, one workgroup per seed (Engine-level: run_ensemble; C ABI:
+    smcmi_run_ensemble) - what a loop of smc(..., seed=s) calls computes, e.g. for the standard deviation of the log-MDD over seeds.
+    Device likelihood families only, n_para <= 10, n_parts <= 8192, alpha = 1, no tempered update.  Returns one (cloud, w, W) per
+    seed, in the order of `seeds`, each as smc() returns it; cloud.status is the member's own code (0: it reached phi = 1)."""
+    from . import _lib
+    from .engine import run_ensemble
+
+    if not isinstance(loglikelihood, DeviceLikelihood):
+        raise NotImplementedError("smc_ensemble() takes a device likelihood (GaussIso, LinReg, LinModel3, CapmLiteral); a Python callable "
+                                  "or a TorchLikelihood runs through smc(), one seed per call")
+    if verbose not in VERBOSITY:
+        raise ValueError("verbose must be one of :none, :low, :high")
+    if resampling_method not in ("systematic", "multinomial", "polyalgo"):
+        raise ValueError("Invalid resampler in SMC. Options are :systematic, :multinomial, or :polyalgo")
+    seeds = [int(s) for s in seeds]
+    if not seeds:
+        raise ValueError("smc_ensemble needs at least one seed")
+    parameters = flatten_regimes(parameters, regime_switching)
+    d = len(parameters)
+    if all(p.fixed for p in parameters):
+        raise AssertionError("All model parameters are fixed!")
+    if d > _lib.ENS_MAX_PARA or n_parts > _lib.ENS_MAX_PARTS or alpha != 1.0:
+        raise NotImplementedError("smc_ensemble() serves n_para <= %d, n_parts <= %d and alpha = 1; smc() serves the rest"
+                                  % (_lib.ENS_MAX_PARA, _lib.ENS_MAX_PARTS))
+    data = np.asarray(data, dtype=np.float64)
+    spec = _spec_from(parameters, loglikelihood.spec(data), None)
+    if max_stages is None:
+        max_stages = n_phi if use_fixed_schedule else 4 * n_phi + 64
+    engines = []
+    try:
+        for s in seeds:
+            e = Engine(n_parts, d, seed=s, device=device, max_stages=max_stages, store_history=True)
+            engines.append(e)
+            e.set_model(spec)
+            e.init_from_prior()
+        rs = run_ensemble(engines, n_blocks=n_blocks, n_mh_steps=n_mh_steps, lam=lam, n_phi=n_phi, resampling_method=resampling_method,
+                          threshold_ratio=threshold_ratio, c=c, alpha=alpha, target=target, use_fixed_schedule=use_fixed_schedule,
+                          tempering_target=tempering_target)
+        out = []
+        for e, r in zip(engines, rs):
+            ns = max(e.stages_held(), 1)
+            rec = e.stage_records(ns)
+            w, W = e.history(ns)
+            cloud = Cloud(d, n_parts)
+            cloud.particles = e.download_cloud()
+            cloud.tempering_schedule = rec["schedule"]
+            cloud.ESS = rec["ess"]
+            cloud.stage_index = ns
+            cloud.n_Phi = n_phi
+            cloud.resamples = r["resamples"]
+            cloud.c = r["c"]
+            cloud.accept = r["accept"]
+            cloud.total_sampling_time = r["seconds"]
+            cloud.logmdd = r["logmdd"]
+            cloud.status = r["status"]
+            out.append((cloud, w, W))
+            if verbose != "none":
+                print(" SMC (seed %d) finished: %d stages, %d resamples, log-MDD = %.6f, status %d" % (e.seed, ns, r["resamples"], r["logmdd"], r["status"]))
+        return out
+    finally:
+        for e in engines:
+            e.close()
+
+
 def _stage_path(savepath, stage):
     """replace(savepath, ".jld2" => "_stage=$(cloud.stage_index).jld2") (src/smc_main.jl:500) for any extension."""
     root, ext = os.path.splitext(savepath if savepath else "smc_cloud.npz")

@@ -574,6 +574,40 @@ def run_group(engines, n_blocks=1, n_mh_steps=1, lam=2.1, n_phi=300, resampling_
     return out
 
 
+def run_ensemble(engines, n_blocks=1, n_mh_steps=1, lam=2.1, n_phi=300, resampling_method="systematic", threshold_ratio=0.5, c=0.5,
+                 alpha=1.0, target=0.25, use_fixed_schedule=True, tempering_target=0.97, prior_weight=0.0, log_prob_old_data=0.0,
+                 solver_passes=0, sync_every=0, use_graph=0, phi_rtol=0.0, initial_ess=0.0, stop_after_stage=0, continue_run=False):
+    """Many small runs in ONE launch, one workgroup per engine (smcmi_run_ensemble): every engine is a whole cloud prepared as for
+    Engine.run - same device, n_para <= 10, n_parts <= 8192, max_stages and store_history; seeds, models and likelihood data may differ.
+    The keywords are Engine.run's.  Returns one result dict per engine, each with its own `status` (0, or the negative code the member
+    failed with: NAN_ESS, POSDEF, CAPACITY, BRACKET - a failing member does not disturb the others) and `call_status`, the code the call
+    returned (0, or the lowest-indexed failing member's).  A call that is refused as a whole (shapes that differ, a shard, a callback,
+    alpha < 1, ...) raises SMCMIError: nothing ran."""
+    engines = list(engines)
+    if not engines:
+        raise ValueError("run_ensemble needs at least one engine")
+    e0 = engines[0]
+    rc = e0._run_config(n_blocks, n_mh_steps, lam, n_phi, resampling_method, threshold_ratio, c, alpha, target, use_fixed_schedule,
+                        tempering_target, prior_weight, log_prob_old_data, solver_passes, sync_every, use_graph, phi_rtol, initial_ess)
+    rc.stop_after_stage, rc.continue_run = int(stop_after_stage), int(bool(continue_run))
+    n = len(engines)
+    res = (_lib.Result * n)()
+    unset = 1                                   # (no member's code is positive: a status still at 1 means the call was refused as a whole)
+    status = (C.c_int32 * n)(*([unset] * n))
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    code = _lib.lib().smcmi_run_ensemble(arr, n, C.byref(rc), res, status)
+    if code != 0 and all(s == unset for s in status):
+        check(code)
+    out = []
+    for k in range(n):
+        r = Engine._result(res[k])
+        r["paused"] = False
+        r["status"] = int(status[k])
+        r["call_status"] = int(code)
+        out.append(r)
+    return out
+
+
 _SUMMARY_ERRORS = {-1: "bad argument: a NaN / negative / infinite weight, weights that sum to zero, a probability outside [0, 1], more than "
                        "MAX_QUANT probabilities, a column that is no parameter, or handles that are not the contiguous shards of one cloud",
                    -2: "a HIP call failed", -7: "this handle holds a shard of its cloud: call the group function with all of its handles"}

@@ -393,6 +393,26 @@ function device_best_particle_group(hs::Vector{Handle}, d::Integer; criterion::S
                         hs, Int32(length(hs)), BEST[criterion], idx, val, para))
     return Int(idx[]) + 1, val[], para
 end
+# Many small runs in ONE launch, one workgroup per handle (include/smcmi.h smcmi_run_ensemble): whole-cloud handles prepared as for smc()'s
+# own run - same device, n_para <= 10, n_parts <= 8192, max_stages, store_history; seeds, models and likelihood data may differ.  Returns
+# (results, status, code): a Result and the member's own code per handle, and the code of the call (0, or the lowest-indexed failing
+# member's).  A call refused as a whole (every status still at its initial 1) throws.
+function run_ensemble(hs::Vector{Handle}, rc::RunConfig)
+    n = length(hs)
+    buf = zeros(UInt8, n * sizeof(Result))              # smcmi_result[n], contiguous as the C side writes them
+    status = ones(Int32, n)
+    results = Vector{Result}(undef, n)
+    code = 0
+    GC.@preserve buf begin
+        base = Ptr{Result}(pointer(buf))
+        code = ccall((:smcmi_run_ensemble, LIB), Cint, (Ptr{Handle}, Int32, Ref{RunConfig}, Ref{Result}, Ptr{Int32}), hs, Int32(n), rc, base, status)
+        code != 0 && all(s -> s == 1, status) && check(code)
+        for k in 1:n
+            results[k] = unsafe_load(base + (k - 1) * sizeof(Result))
+        end
+    end
+    return results, status, Int(code)
+end
 # parity aid: (θ̄, R) the last stage used for its proposals, as the engine left them (row-major on the C side; R before (R + R') / 2)
 function stage_moments(h::Handle, d::Integer)
     m = Vector{Float64}(undef, d); R = Matrix{Float64}(undef, d, d)
