@@ -957,7 +957,10 @@ __host__ __device__ constexpr int cm_pair_b(int da, int idx) {
     while (k >= da - a) { k -= da - a; ++a; }
     return a + k;
 }
-template <int D, int NW, class ST>
+// DEADZERO (the segment kernel, stage3.hpp K3H_DEAD): the caller vouches that a lane with !live holds v == +0.0 and xx[0..D] == +0.0.  Its
+// sums are then +0.0 without the select: v = +0, v v = +0 · +0 = +0, (v xx[a]) xx[b] = (+0 · +0) · +0 = +0 - the product of two zeros of
+// equal sign is +0 in every rounding mode, so the bits `live ? val : 0.0` would give.  Live lanes: the same operations either way.
+template <int D, int NW, bool DEADZERO = false, class ST>
 __device__ inline void k2_cm_row_one(double v, const double (&xx)[D + 1], bool live, double *red, ST store) {
     constexpr int DA = D + 1, NPF = DA * (DA + 1) / 2 + 2;
     cm_row_chunks<NPF, NW>(red, [&](auto C, double (&a)[CMW]) __attribute__((always_inline)) {
@@ -972,7 +975,8 @@ __device__ inline void k2_cm_row_one(double v, const double (&xx)[D + 1], bool l
                 const double wx = v * xx[pa];
                 val = wx * xx[pb];
             }
-            a[q] = live ? val : 0.0;
+            if constexpr (DEADZERO) a[q] = val;
+            else a[q] = live ? val : 0.0;
         });
     }, store);
 }

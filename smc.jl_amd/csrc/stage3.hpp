@@ -397,15 +397,19 @@ __device__ inline bool gather_totals_pair(const unsigned long long *tbl_m, unsig
 #define K3H_SW 2                  // the schedule window of stage n + 1's begin is filled behind stage n's Post2, under the hand-over, not in begin_stage
 #define K3H_REDRAW 4              // a stage that resampled inside the segment draws its parked random numbers again UNDER the selection's second hand-over, not behind it
 #define K3H_GATHER 8              // a gatherer's sweeps of the correction and the mutation rows through k3_gather (below) instead of gather_vshard
+// ... and the per-particle phases' vector instructions the result does not need (same rule: no operation on a live value, or its order, moves)
+#define K3H_DEAD 16               // α = 1: the correction row's sums without the `live` select - a dead lane's operands are +0.0 (k2_cm_row_one DEADZERO)
+#define K3H_LIVE 32               // α = 1: the worker's `live` mask from a flag in a vector register where it is used (one v_cmp), not carried across the loop in spilled scalars
 #ifndef SMCMI_K3HO
-#define SMCMI_K3HO (K3H_FETCH | K3H_SW | K3H_REDRAW | K3H_GATHER)
+#define SMCMI_K3HO (K3H_FETCH | K3H_SW | K3H_REDRAW | K3H_GATHER | K3H_DEAD | K3H_LIVE)
 #endif
 #if defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1 && SMCMI_INST3_A != 0
 #define K3HO (SMCMI_K3HO)
 #elif defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1
 // (the mixture kernel: with the redraw inside k3_select_inside its scratch grows from 64 to 80 bytes per lane at n_para 10, past the bound
-// tests/test_abi_cpu.py holds it to; its redraw stays where it was)
-#define K3HO ((SMCMI_K3HO) & ~K3H_REDRAW)
+// tests/test_abi_cpu.py holds it to; its redraw stays where it was.  K3H_DEAD does not reach it - its row goes through accumulators - and
+// K3H_LIVE left its headline where it was, 8.24 ms per step either way: the mixture units keep their parent's device code)
+#define K3HO ((SMCMI_K3HO) & ~(K3H_REDRAW | K3H_DEAD | K3H_LIVE))
 #else
 #define K3HO 0
 #endif
@@ -824,6 +828,13 @@ __device__ inline void k3_leave_note(const Seg3Args &sa, const Ctl2 *ctl) {
             (prof)[(slot)] = (long long)tt_;                                                                                   \
         }                                                                                                                     \
     } while (0)
+
+// a lane's flag, kept in a vector register, as a predicate formed HERE (K3H_LIVE: the empty asm is opaque to the compiler, so the compare
+// cannot move in front of it - out of a loop, into a scalar register pair that lives across it)
+__device__ __forceinline__ bool k3_lane_flag(int &f) {
+    asm volatile("" : "+v"(f));
+    return f != 0;
+}
 
 // grid = g.Vl * g.nb2 blocks of T3 threads, every one resident; block b owns block (b / Vl) of local virtual shard (b % Vl): with the
 // hardware's round-robin of consecutive blocks over the 8 XCDs a virtual shard's blocks share an XCD (its rows are totalled out of
@@ -1480,7 +1491,23 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         for (int k = 0; k < D; ++k) x[k] = 0.0;
         like = lprior = like_prev = 0.0;
     }
+#if (K3HO) & K3H_LIVE
+    // K3H_LIVE: `live` is a predicate of tid - the compiler forms it once, in front of the stage loop, and the loop, which has no scalar
+    // register to spare, spills the mask into lanes of a vector register and reads it back (two v_readlane and a wait) at every use.  As a
+    // flag in a vector register it is one v_cmp at the use; the empty asm keeps the compare from being hoisted again.  The same predicate.
+    int live_v = live ? 1 : 0;
+#define K3_LIVE k3_lane_flag(live_v)
+#define K3_LIVE_ROW_DECL const bool live_r = k3_lane_flag(live_v)      /* (one compare for the mutation row's three uses) */
+#define K3_LIVE_ROW live_r
 #else
+#define K3_LIVE live
+#define K3_LIVE_ROW_DECL (void)0
+#define K3_LIVE_ROW live
+#endif
+#else
+#define K3_LIVE live
+#define K3_LIVE_ROW_DECL (void)0
+#define K3_LIVE_ROW live
     const int vl = (int)blockIdx.x % g.Vl, wr = (int)blockIdx.x / g.Vl;
     const double pw = rp.pw, logp_old = rp.logp_old, nrm_N = ma.n_parts;
     const bool hist = rp.store_history && sa.hist_w != nullptr;
@@ -1592,7 +1619,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
                 double xx[D + 1];
 #pragma unroll
                 for (int a = 0; a <= D; ++a) xx[a] = 0.0;
-                if (live) {
+                if (K3_LIVE) {
                     double inc;
                     v = k2_cm_weight<D>([&](int a) { return x[a]; }, po.shift, like, like_prev, Wt, esh, phi, phi_prev, pw, logp_old, xx, &inc);
                     if (hist) {
@@ -1600,7 +1627,9 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
                         sa.hist_w[(long long)(n - 1) * sa.hist_ld + i] = inc * unshift;
                     }
                 }
-                k2_cm_row_one<D, T3 / 64>(v, xx, live, red, [&](int idx, double val) { if (K3_HAS) gran_store(my_cm + idx * 2, val, tag); });
+                // (K3H_DEAD: a dead lane holds v == +0.0 - set above, k2_cm_weight ran under `live` only, and the entered stage, whose v is K1's,
+                // forms no row - and xx[0..D] == +0.0, zeroed above: the sums need no select, stage2.hpp DEADZERO)
+                k2_cm_row_one<D, T3 / 64, ((K3HO) & K3H_DEAD) != 0>(v, xx, K3_LIVE, red, [&](int idx, double val) { if (K3_HAS) gran_store(my_cm + idx * 2, val, tag); });
             } else {
                 // (the mixture kernel: the same sums, same bits, through the accumulator form - its register allocation takes that better:
                 // 115 against 164 scratch reloads in the stage loop, 48.7 against 59.8 µs per stage)
@@ -1608,7 +1637,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
                 double acc[NCH * 64];
 #pragma unroll
                 for (int q = 0; q < NCH * 64; ++q) acc[q] = 0.0;
-                if (live) {
+                if (K3_LIVE) {
                     double inc;
                     v = k2_cm_particle<D>(acc, [&](int a) { return x[a]; }, po.shift, like, like_prev, Wt, esh, phi, phi_prev, pw, logp_old, &inc);
                     if (hist) {
@@ -1745,18 +1774,19 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
 #pragma unroll
             for (int e = 0; e < D; ++e) z[e] = p[(2 + e) * T3];
         } else mh_draw<D>(ma.seed, pid, (unsigned)n, 0u, db0, step_prob, uc, z);       // (only chunk 0's first proposal is drawn ahead)
-        if (live) {
+        if (K3_LIVE) {
             Wt = rs ? 1.0 : (v * nrm_N) / nrm_sumw;             // W·N then /ΣW̃, two roundings like the reference (particle.jl:362-366); 1 after a resample
             if (ma.hist_W && ma.store_history) ma.hist_W[(long long)(n - 1) * ma.hist_ld + i] = Wt;
         }
-        k2_mh_steps<D, ALPHA1, T3, true, false, FAST>(L, mixbuf, mixpos, mixzt, ma, g.n, lv, mv, nb, nf, live, i, pid, (unsigned)n, phi_n, x, like, lprior, like_prev, accept,
+        k2_mh_steps<D, ALPHA1, T3, true, false, FAST>(L, mixbuf, mixpos, mixzt, ma, g.n, lv, mv, nb, nf, K3_LIVE, i, pid, (unsigned)n, phi_n, x, like, lprior, like_prev, accept,
                                          step_prob, uc, z);
-        if (live) acc_val = accept / (double)nf;                // quirk Q2: normalised by n_free only
+        if (K3_LIVE) acc_val = accept / (double)nf;             // quirk Q2: normalised by n_free only
         K3_STAMP(sa.prof, 5);
         {
             double *plain = ma.rows_mut + (long long)rowi * RMUT;      // (the launch after this one totals the last stage's rows from here)
             unsigned long long *my_mut = sa.g_mut + K3_RPAR(n) + (long long)rowi * RMUT * 2;
-            k2_mut_row_f<T3>(ma.adaptive != 0, like, like_prev, live ? Wt : 0.0, live ? acc_val : 0.0, e_center, live, rs != 0, red, L.red,
+            K3_LIVE_ROW_DECL;
+            k2_mut_row_f<T3>(ma.adaptive != 0, like, like_prev, K3_LIVE_ROW ? Wt : 0.0, K3_LIVE_ROW ? acc_val : 0.0, e_center, K3_LIVE_ROW, rs != 0, red, L.red,
                              [&](int idx, double val) { if (K3_HAS) { gran_store(my_mut + idx * 2, val, tag); plain[idx] = val; } },
                              energy_base(like_prev, rp.pw, rp.logp_old));
             if (K3_HAS && tid == RMUT - 1) gran_store(my_mut + tid * 2, 0.0, tag);                  // (column 33 is unused)
@@ -1774,6 +1804,9 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         }
     }
 #undef K3_RPAR
+#undef K3_LIVE
+#undef K3_LIVE_ROW_DECL
+#undef K3_LIVE_ROW
 #undef K3_FILL_SW
 #undef K3_TOTALS_CM
 #undef K3_TOTALS_MUT
