@@ -224,6 +224,19 @@ def resample(weights, method="systematic", seed=0, stage=0, n_parts=None, offset
     return idx
 
 
+_TAG_P_RES = 1 << 28          # TAG(P_RES, 0, 0) of smc_oracle.c: purpose P_RES = 1 in bits 28 .. 31, t = q = 0
+
+
+def resample_offsets(method, n_parts, seed=0, stage=0):
+    """The Philox offsets orc_resample draws: one per slot (multinomial) or one (systematic)."""
+    ua, ub = C.c_double(), C.c_double()
+    out = np.empty(n_parts if RESAMPLE[method] == 1 else 1)
+    for i in range(out.size):
+        lib().orc_uniform_pair(C.c_uint64(seed), C.c_uint64(i), C.c_uint32(stage), C.c_uint32(_TAG_P_RES), C.byref(ua), C.byref(ub))
+        out[i] = ua.value
+    return out
+
+
 def weighted_mean(particles):
     p = fcloud(particles)
     out = np.empty(p.shape[1] - 5)

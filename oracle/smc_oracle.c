@@ -433,8 +433,15 @@ void orc_correct(double *particles, int64_t n, int32_t R, double phi_n, double p
     *sum_unnorm = s;
 }
 
-/* ref: src/resample.jl:23-72.  Output indices 0-based.  Fall-through (reference returns 0 / nothing,
-   reachable only through round-off) is clamped to the last index - the one documented deviation. */
+/* ref: src/resample.jl:23-72.  Output indices 0-based.  The selection rule, the one documented deviation: if the
+   search falls through (the reference returns 0 / nothing; reachable only through round-off - a threshold that
+   rounds to 1.0, a cum column that ends below 1) or the row found has weight 0, the ancestor is the nearest row
+   before it with positive weight.  (The sequential cum below never steps across a zero-weight row, so here only
+   the fall-through acts; the device's tree scans can, and follow the same rule.) */
+static int64_t last_positive_row(const double *weights, int64_t j) {
+    while (j > 0 && !(weights[j] > 0.0)) --j;
+    return j;
+}
 void orc_resample_with_offsets(const double *weights, int64_t nw, int64_t n_parts, int32_t method,
                                const double *offsets, int64_t *idx) {
     double *cw = (double *)malloc(sizeof(double) * nw), s = 0.0, run = 0.0;
@@ -444,7 +451,7 @@ void orc_resample_with_offsets(const double *weights, int64_t nw, int64_t n_part
         for (int64_t i = 0; i < n_parts; ++i) {                                  /* resample.jl:38-41 */
             int64_t f = -1;
             for (int64_t jx = 0; jx < nw; ++jx) if (offsets[i] < cw[jx]) { f = jx; break; }
-            idx[i] = f < 0 ? nw - 1 : f;
+            idx[i] = last_positive_row(weights, f < 0 ? nw - 1 : f);
         }
     } else {
         double offset = offsets[0];
@@ -453,7 +460,7 @@ void orc_resample_with_offsets(const double *weights, int64_t nw, int64_t n_part
             double thr = ((double)i + offset) / (double)n_parts;                /* (i - 1 + offset)/n_parts, 1-based i */
             int64_t f = -1;
             for (int64_t jx = start; jx < lim; ++jx) if (cw[jx] > thr) { f = jx; break; }
-            if (f < 0) f = lim - 1;
+            f = last_positive_row(weights, f < 0 ? lim - 1 : f);
             idx[i] = f;
             start = f;
         }

@@ -272,7 +272,8 @@ __global__ void __launch_bounds__(ENS_T) kens_run(EnsArgs a) {
             __syncthreads();
             double run = incl - local;
             for (int w = 0; w < wave; ++w) run += red[w];
-            for (long long p = beg; p < end; ++p) { run += (wv[p] / N) / ssum; wv[p] = run; }
+            // (a row of weight 0 keeps its cum value with the sign bit set: the selection rule below needs to know it, and wv is all there is)
+            for (long long p = beg; p < end; ++p) { const double w0 = wv[p]; run += (w0 / N) / ssum; wv[p] = w0 > 0.0 ? run : -run; }
             __syncthreads();
             double u_sys = 0.0, ub_ = 0.0;
             if (rp.resampling_method != SMCMI_RESAMPLE_MULTINOMIAL) uniform_pair(seed, 0ull, (unsigned)i, rng_tag(P_RES, 0, 0), u_sys, ub_);
@@ -285,9 +286,10 @@ __global__ void __launch_bounds__(ENS_T) kens_run(EnsArgs a) {
                 long long lo = 0, hi = n;                                     // first index with cum > thr
                 while (lo < hi) {
                     const long long mid = (lo + hi) >> 1;
-                    if (wv[mid] > thr) hi = mid; else lo = mid + 1;
+                    if (fabs(wv[mid]) > thr) hi = mid; else lo = mid + 1;
                 }
-                const long long anc = lo < n ? lo : n - 1;
+                long long anc = lo < n ? lo : n - 1;                         // the selection rule (kernels.hpp select_rule): a fall-through or a
+                while (anc > 0 && __builtin_signbit(wv[anc])) --anc;                   // row of weight 0 takes the nearest row before it with positive weight
 #pragma unroll
                 for (int k = 0; k < D + 3; ++k) other[(long long)k * n + p] = cloud[(long long)k * n + anc];
             }

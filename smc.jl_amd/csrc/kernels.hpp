@@ -1238,19 +1238,29 @@ static __global__ void __launch_bounds__(TB) k_scan_weights(CloudPtrs cl, const 
 }
 #endif
 
+// The selection rule: a search that fell through (the reference returns index 0 / nothing; reachable only by
+// round-off - a threshold that rounds to 1.0, a cum column that ends an ulp below it) or that found a row of weight 0 (a
+// tree-scanned cum column can step up by an ulp across one) takes the nearest row before it with positive weight.
+// w: the weights the cum column was scanned from; lo: the upper_bound's result in [first, n]; rows below `first` are not held.
+__device__ inline long long select_rule(const double *w, long long lo, long long n, long long first = 0) {
+    long long a = lo < n ? lo : n - 1;
+    while (a > first && !(w[a] > 0.0)) --a;
+    return a;
+}
 // Selection for output slot k: ancestor = first j with cum[j] > thr (src/resample.jl:51-70 systematic walk, :33-41
-// multinomial findfirst; fall-through, which the reference turns into index 0 / nothing and is reachable only by
-// round-off, clamps to the last index), then cloud.particles = particles[new_inds, :] and reset_weights!
+// multinomial findfirst) under the selection rule above, then cloud.particles = particles[new_inds, :] and reset_weights!
 // (src/smc_main.jl:440-442): the thread copies its ancestor's R-1 columns into the other cloud buffer and sets W = 1.
 // full != nullptr: rows come from an all-gathered n_cum x R cloud (multi-GPU) and go to the current buffer.
+// wsel: the n_cum weights behind `cum` (nullptr: the current buffer's weight column; callers with `full` pass the gathered weights).
 #ifndef SMCMI_INST_UNIT
 static __global__ void __launch_bounds__(TB) k_resample_gather(CloudPtrs cl, const DevState *st, const double *cum, long long n_cum,
                                                         long long slot0, long long n_parts_total, int method,
                                                         unsigned long long seed, unsigned stage, const double *offsets,
                                                         long long *anc, const double *full, int force, long long full_shard_n = 0,
-                                                        int dst_buf = -1) {
+                                                        int dst_buf = -1, const double *wsel = nullptr) {
     if (!force && (st->done || !st->do_resample)) return;
     if (!force) stage = (unsigned)st->stage;
+    if (!wsel) wsel = col(cl, st->cur, cl.R - 1);
     for (long long k = (long long)blockIdx.x * TB + threadIdx.x; k < cl.n; k += (long long)gridDim.x * TB) {
     const long long slot = slot0 + k;
     double ua, ub;
@@ -1267,7 +1277,7 @@ static __global__ void __launch_bounds__(TB) k_resample_gather(CloudPtrs cl, con
         const long long mid = (lo + hi) >> 1;
         if (cum[mid] > ua) hi = mid; else lo = mid + 1;
     }
-    const long long a = lo < n_cum ? lo : n_cum - 1;
+    const long long a = select_rule(wsel, lo, n_cum);
     if (anc) anc[k] = a;
     const int src = st->cur, dst = dst_buf >= 0 ? dst_buf : (full ? src : (src ^ 1)), R = cl.R;
     // source row: the local buffer, an n_cum x R column-major cloud, or (full_shard_n > 0) the concatenation of per-rank
@@ -1319,7 +1329,7 @@ static __global__ void __launch_bounds__(TB) k_bridge_gather(CloudPtrs src, int 
         const long long mid = (lo + hi) >> 1;
         if (cum[mid] > ua) hi = mid; else lo = mid + 1;
     }
-    const long long a = lo < lim ? lo : lim - 1;
+    const long long a = select_rule(col(src, src_buf, src.R - 1), lo, lim);
     if (anc) anc[k] = a;
     for (int c = 0; c < src.R; ++c) col(dst, dst_buf, c)[k] = col(src, src_buf, c)[a];
 }
@@ -1346,10 +1356,11 @@ static __global__ void __launch_bounds__(TB) k_normalize_weights(CloudPtrs cl, c
 
 // Systematic resampling, sharded: ancestor (global row) of the first and of the last output slot of every shard r - the rows a
 // shard must receive form the contiguous range [out[2r], out[2r+1]] (thresholds ascend with the slot).  Same threshold and
-// upper_bound as k_resample_gather.  out[0] = -1 when this stage does not resample.  One wavefront, lane r = shard r.
+// upper_bound and selection rule as k_resample_gather (wsel: the all-gathered weights).  out[0] = -1 when this stage does not
+// resample.  One wavefront, lane r = shard r.
 #ifndef SMCMI_INST_UNIT
 static __global__ void k_anc_ranges(const DevState *st, const double *cum, long long N, long long n_local, int world, unsigned long long seed,
-                             long long *out) {
+                             long long *out, const double *wsel) {
     const int r = threadIdx.x;
     if (st->done || !st->do_resample) { if (r == 0) out[0] = -1; return; }
     if (r >= world) return;
@@ -1363,7 +1374,7 @@ static __global__ void k_anc_ranges(const DevState *st, const double *cum, long 
             const long long mid = (lo + hi) >> 1;
             if (cum[mid] > thr) hi = mid; else lo = mid + 1;
         }
-        out[2 * r + e] = lo < N ? lo : N - 1;
+        out[2 * r + e] = select_rule(wsel, lo, N);
     }
 }
 #endif

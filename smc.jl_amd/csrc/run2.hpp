@@ -457,7 +457,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
                 Eng2 *e = h->e2;
                 const Rows2 cr = cm_rows(h);
                 k2_scan<<<g0.V * g0.nb1, TS, 0, h->stream>>>(e->d_ctl, h->d_st, e->g, n, cr, h->d_wt, e->csum, h->d_cum);
-#define SMCMI_CALL(D) launch_k2_gather<D>(h, n, cr, h->d_cum, rc->resampling_method, nullptr, 0, -1)
+#define SMCMI_CALL(D) launch_k2_gather<D>(h, n, cr, h->d_cum, rc->resampling_method, nullptr, 0, -1, h->d_wt)
                 SMCMI_D_SWITCH(d, SMCMI_CALL)
 #undef SMCMI_CALL
             }
@@ -520,7 +520,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
                 const Rows2 cr = cm_rows(h);
                 const int me = g.rccl ? h->rank : shard_rank(h);
                 const long long s_lo = a2a ? ranges[2 * me] : 0, s_hi = a2a ? ranges[2 * me + 1] : -1;
-#define SMCMI_CALL(D) launch_k2_gather<D>(h, n, cr, h->d_cum_full, rc->resampling_method, h->d_full_cloud, s_lo, s_hi)
+#define SMCMI_CALL(D) launch_k2_gather<D>(h, n, cr, h->d_cum_full, rc->resampling_method, h->d_full_cloud, s_lo, s_hi, a2a ? nullptr : h->d_full_w)
                 SMCMI_D_SWITCH(d, SMCMI_CALL)
 #undef SMCMI_CALL
             }

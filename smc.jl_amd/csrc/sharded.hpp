@@ -436,7 +436,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     auto gather_full = [&](smcmi_handle *h) {
         const long long N = h->cfg.n_parts;
         k_resample_gather<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_cum_full, N, h->cfg.gid0, N, rc->resampling_method,
-                                                                                h->cfg.seed, 0u, nullptr, h->d_anc, h->d_full_cloud, 0, h->n, 1);
+                                                                                h->cfg.seed, 0u, nullptr, h->d_anc, h->d_full_cloud, 0, h->n, 1, h->d_full_w);
     };
     // proposal set-up from the all-reduced moments, the mutation, and what the next begin reads of it totalled over all shards
     auto mutate_and_reduce = [&](int prep_mode, int fin_slot) -> int {
@@ -545,7 +545,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
                 for (auto *h : g.hs) {
                     HIP_TRY(hipSetDevice(h->cfg.device));
                     scan_full(h);
-                    k_anc_ranges<<<1, 64, 0, h->stream>>>(h->d_st, h->d_cum_full, h->cfg.n_parts, h->n, g.world, h->cfg.seed, h->d_anc);
+                    k_anc_ranges<<<1, 64, 0, h->stream>>>(h->d_st, h->d_cum_full, h->cfg.n_parts, h->n, g.world, h->cfg.seed, h->d_anc, h->d_full_w);
                 }
                 std::vector<long long> ranges(2 * (size_t)g.world);
                 HIP_TRY(hipSetDevice(h0->cfg.device));

@@ -1192,7 +1192,7 @@ extern "C" int smcmi_shard_resample(smcmi_handle *h, const double *dev_full_weig
     k_chunk_offsets<<<1, 1, 0, h->stream>>>(h->d_st, h->d_part_full, h->nb_full, h->d_off_full, 0.0, 1);
     k_scan_weights<<<h->nb_full, TB, 0, h->stream>>>(wcl, h->d_st, h->d_off_full, h->d_cum_full, 1, h->nb_full);
     k_resample_gather<<<(unsigned)((h->n + TB - 1) / TB), TB, 0, h->stream>>>(h->cl, h->d_st, h->d_cum_full, N, h->cfg.gid0, N, method,
-                                                                            h->cfg.seed, stage, nullptr, h->d_anc, dev_full_cloud, 1);
+                                                                            h->cfg.seed, stage, nullptr, h->d_anc, dev_full_cloud, 1, 0, -1, dev_full_weights);
     if (ancestors_out) HIP_TRY(hipMemcpyAsync(ancestors_out, h->d_anc, sizeof(long long) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;

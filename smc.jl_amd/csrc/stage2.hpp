@@ -1245,14 +1245,16 @@ static __global__ void k2_owner_ranges(Ctl2 *ctl, const DevState *st, int n, Row
 #endif
 
 // ------------------------------------------------------------------------------------------------ selection: gather + moments
-// Output slot k: ancestor = first j with cum[j] > threshold (src/resample.jl:33-70; fall-through clamps to the last index), its
+// Output slot k: ancestor = first j with cum[j] > threshold (src/resample.jl:33-70) under the selection rule of kernels.hpp select_rule
+// (wsel: the weights behind `cum`, indexed like it; nullptr - a sharded exchange that moved only cum values and rows - clamps to the last row), its
 // R-1 columns are copied into cloud buffer 1 (K2 reads the resampled cloud from there and writes buffer 0), and the moments of
 // the resampled cloud (all weights 1; smc_main.jl:440-446, 457-465) are accumulated on the way -> one row of pair sums per block.
 // full: rows come from the per-handle [R][full_shard_n] shard buffers of an exchange (sharded runs), else from buffer 0.
 template <int D>
 __global__ void __launch_bounds__(TB) k2_gather_wide(CloudPtrs cl, Ctl2 *ctl, const DevState *st, Geo2 g, int n, Rows2 cmrows, const double *cum,
                                                 int method, unsigned long long seed, long long gid0, long long *anc, const double *full,
-                                                long long full_shard_n, double *rows_gm, long long s_lo = 0, long long s_hi = -1) {
+                                                long long full_shard_n, double *rows_gm, long long s_lo = 0, long long s_hi = -1,
+                                                const double *wsel = nullptr) {
     constexpr int DA = D + 1, NP = DA * (DA + 1) / 2, NCH = (NP + 63) / 64;
     __shared__ double red[(TB / 64) * 64];
     __shared__ double s_vt[V2_MAXV * 2 * 8], s_tot[2];
@@ -1280,6 +1282,7 @@ __global__ void __launch_bounds__(TB) k2_gather_wide(CloudPtrs cl, Ctl2 *ctl, co
     // (s_lo .. s_hi: the global rows whose cum this handle holds - a sharded run exchanges only its slots' ancestor range)
     const long long s_end = s_hi < 0 ? N : s_hi + 1;
     auto gather_row = [&](long long a, long long k) {
+        if (wsel) a = select_rule(wsel, a, s_end, s_lo);       // (kernels.hpp: the selection rule)
         if (anc) anc[k] = a;
         const double *from = cl.buf[0];
         long long ldf = cl.n, a_row = a;
@@ -1376,7 +1379,10 @@ __global__ void __launch_bounds__(TB) k2_gather_wide(CloudPtrs cl, Ctl2 *ctl, co
 
 // The same for n_para <= 10 by blocks of TS = 512 threads, one output slot per thread and tile - built from functions a worker of a
 // persistent segment (stage3.hpp: 512 particles, one per thread) calls on its own slots, so that a segment that resamples without
-// leaving selects the ancestors and leaves the moment row this kernel leaves, bit for bit.
+// leaving selects the ancestors and leaves the moment row this kernel leaves, bit for bit.  The selection rule (kernels.hpp select_rule) is
+// applied by each caller to what sel_search_tile returns: here from the weights (wsel), in the segment from the sign bit of its cum column -
+// the same row either way.  The one path without it is several handles under the all-to-all-v exchange (wsel == nullptr: the clamp to the
+// last row of the received range): there, in the event, a launch can pick another ancestor than one handle or a segment would.
 constexpr int SEL_GCH = 512, SEL_NC = 2048, SEL_CAP = 4096;
 // threshold of global output slot `slot` (src/resample.jl:33-70)
 __device__ inline double sel_threshold(int method, unsigned long long seed, long long slot, int n, double u_sys, long long N) {
@@ -1446,7 +1452,8 @@ __device__ inline void sel_moment_row(const double (&acc)[(D + 1) * (D + 2) / 2]
 template <int D>
 __global__ void __launch_bounds__(TS) k2_gather(CloudPtrs cl, Ctl2 *ctl, const DevState *st, Geo2 g, int n, Rows2 cmrows, const double *cum,
                                                 int method, unsigned long long seed, long long gid0, long long *anc, const double *full,
-                                                long long full_shard_n, double *rows_gm, long long s_lo = 0, long long s_hi = -1) {
+                                                long long full_shard_n, double *rows_gm, long long s_lo = 0, long long s_hi = -1,
+                                                const double *wsel = nullptr) {
     constexpr int DA = D + 1, NP = DA * (DA + 1) / 2;
     __shared__ double red[(TS / 64) * cm_row_ld(NP)];
     __shared__ double s_vt[V2_MAXV * 2 * 8], s_tot[2];
@@ -1486,8 +1493,9 @@ __global__ void __launch_bounds__(TS) k2_gather(CloudPtrs cl, Ctl2 *ctl, const D
         const bool live = k < end;
         const long long slot = gid0 + (live ? k : end - 1);                  // (a dead thread stands for the tile's last live slot)
         const double ua = sel_threshold(method, seed, slot, n, u_sys, N);
-        const long long a = sel_search_tile(ua, staged, nc, s_ce, s_cw, s_r, ldcum, s_lo, s_end);
+        long long a = sel_search_tile(ua, staged, nc, s_ce, s_cw, s_r, ldcum, s_lo, s_end);
         if (!live) continue;
+        if (wsel) a = select_rule(wsel, a, s_end, s_lo);       // (kernels.hpp: the selection rule)
         if (anc) anc[k] = a;
         const double *from = cl.buf[0];
         long long ldf = cl.n, a_row = a;

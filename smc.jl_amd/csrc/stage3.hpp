@@ -926,7 +926,10 @@ __device__ __attribute__((noinline)) int k3_select_inside(const Sel3Args *selp, 
     {
         double tt;
         const double incl = sel_tile_scan(live ? sto[tid] : 0.0, s_w, &tt);
-        const double cv = (s_off[(sys ? sl.chunk0 : 0) + rowi] + incl) / s_tot[0];
+        // (the selection rule, kernels.hpp select_rule: a row of weight 0 keeps its cum value with the sign bit set - the weights of other
+        // workers' particles are nowhere in memory, the cum column is; the searches below compare fabs)
+        const double cv0 = (s_off[(sys ? sl.chunk0 : 0) + rowi] + incl) / s_tot[0];
+        const double cv = (live && sto[tid] > 0.0) ? cv0 : -cv0;
         if (live) {
             if (sys) {
                 for (int pr = 0; pr < sl.world; ++pr)
@@ -948,13 +951,15 @@ __device__ __attribute__((noinline)) int k3_select_inside(const Sel3Args *selp, 
     // (5) ancestors of my output slots
     double u_sys = 0.0, ub_;
     if (sl.method != SMCMI_RESAMPLE_MULTINOMIAL) uniform_pair(seed, 0ull, (unsigned)n, rng_tag(P_RES, 0, 0), u_sys, ub_);
-    auto ldcum = [&](long long j) { return load_f64_sc1(cum_rsrc, (unsigned)j * 8u); };
+    auto ldcum = [&](long long j) { return fabs(load_f64_sc1(cum_rsrc, (unsigned)j * 8u)); };
     const bool staged = sl.method != SMCMI_RESAMPLE_MULTINOMIAL && ncg <= 1024 && cap_w >= 2 * SEL_GCH;
     if (staged) sel_chunk_ends(ldcum, 0, Ng, ncg, s_ce);
     K3S(5);
     const long long slot = gid0 + (live ? i : (end > beg ? end - 1 : 0));
     const double ua = sel_threshold(sl.method, seed, slot, n, u_sys, Ng);
-    const long long anc_i = (end > beg) ? sel_search_tile(ua, staged, ncg, s_ce, s_cw, s_r, ldcum, 0, Ng, cap_w) : 0;
+    long long anc_i = (end > beg) ? sel_search_tile(ua, staged, ncg, s_ce, s_cw, s_r, ldcum, 0, Ng, cap_w) : 0;
+    if (live)                                                       // a row of weight 0 (or a fall-through's last row): the nearest row before it with weight
+        while (anc_i > 0 && __builtin_signbit(load_f64_sc1(cum_rsrc, (unsigned)anc_i * 8u))) --anc_i;
     K3S(6);
     // (6) the ancestor's row becomes my particle (several handles: out of the rows of the handle that holds it - one buffer descriptor per
     // handle some lane of the wavefront reads from; a tile's ancestors are consecutive rows, so that is one handle, two at a boundary)
@@ -1079,7 +1084,8 @@ __device__ __attribute__((noinline)) int k3_select_two(const Sel3Args *selp, dou
         const bool live = ci[q] < ch[q].end;
         double tt;
         const double incl = sel_tile_scan(live ? ch[q].wv[tid] : 0.0, s_w, &tt);
-        if (live) row_store(sl.cum + ci[q], (s_off[ch[q].rowi] + incl) / s_tot[0], true);
+        const double cv0 = (s_off[ch[q].rowi] + incl) / s_tot[0];     // (weight 0: the sign bit set, see k3_select_inside)
+        if (live) row_store(sl.cum + ci[q], ch[q].wv[tid] > 0.0 ? cv0 : -cv0, true);
     }
     // (4) hand-over: every store above is acknowledged before this block says so
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1091,7 +1097,7 @@ __device__ __attribute__((noinline)) int k3_select_two(const Sel3Args *selp, dou
     // (5) ancestors of the output slots, (6) their rows become the particles
     double u_sys = 0.0, ub_;
     if (sl.method != SMCMI_RESAMPLE_MULTINOMIAL) uniform_pair(seed, 0ull, (unsigned)n, rng_tag(P_RES, 0, 0), u_sys, ub_);
-    auto ldcum = [&](long long j) { return load_f64_sc1(cum_rsrc, (unsigned)j * 8u); };
+    auto ldcum = [&](long long j) { return fabs(load_f64_sc1(cum_rsrc, (unsigned)j * 8u)); };
     const bool staged = sl.method != SMCMI_RESAMPLE_MULTINOMIAL && ncg <= 1024 && cap_w >= 2 * SEL_GCH;
     if (staged) sel_chunk_ends(ldcum, 0, Ng, ncg, s_ce);
     double xx[2][DAm];
@@ -1106,8 +1112,9 @@ __device__ __attribute__((noinline)) int k3_select_two(const Sel3Args *selp, dou
         const long long slot = gid0 + (live ? i : (end > beg ? end - 1 : 0));
         const double ua = sel_threshold(sl.method, seed, slot, n, u_sys, Ng);
         __syncthreads();                                            // (the previous chunk's search is done with s_r / s_cw)
-        const long long anc_i = (end > beg) ? sel_search_tile(ua, staged, ncg, s_ce, s_cw, s_r, ldcum, 0, Ng, cap_w) : 0;
+        long long anc_i = (end > beg) ? sel_search_tile(ua, staged, ncg, s_ce, s_cw, s_r, ldcum, 0, Ng, cap_w) : 0;
         if (live) {
+            while (anc_i > 0 && __builtin_signbit(load_f64_sc1(cum_rsrc, (unsigned)anc_i * 8u))) --anc_i;     // the selection rule
             if (sl.anc) sl.anc[i] = anc_i;
             double row[D + 4];
 #pragma unroll

@@ -43,9 +43,15 @@ def main():
         for rep in range(cfg.get("reps", 1)):
             if rep:
                 eng.init_from_prior()
+            if cfg.get("upload"):                      # a cloud the test wrote (n x R .npy): this rank's rows replace the prior draw
+                nl = n // world
+                eng.upload_cloud(np.asfortranarray(np.load(cfg["upload"])[rank * nl:(rank + 1) * nl]))
             kw = dict(cfg["kw"])
             stop = kw.pop("pause_at", 0)
-            if stop:                                   # pause at a save point, then continue in place (smc_main.jl:499-507)
+            if cfg.get("stop_at"):                     # one bracket: the run ends at its pause (tests/test_gpu_select_range.py)
+                r = shd.run(eng, stop_after_stage=cfg["stop_at"], **kw)
+                assert r["paused"], r
+            elif stop:                                 # pause at a save point, then continue in place (smc_main.jl:499-507)
                 r = shd.run(eng, stop_after_stage=stop, **kw)
                 assert r["paused"], r
                 r = shd.run(eng, continue_run=True, **kw)
@@ -62,6 +68,8 @@ def main():
                              segment_stages=r.get("segment_stages", 0), shift_fallback_stage=r.get("shift_fallback_stage", 0)))
             if cfg.get("full_records"):
                 runs[-1]["schedule_values"] = [float(x) for x in rec["schedule"]]
+                runs[-1]["resampled_values"] = [int(x) for x in rec["resampled"]]
+                runs[-1]["accept_values"] = [float(x) for x in rec["accept_hist"]]
         np.save(os.path.join(out, "cloud%d.npy" % rank), cloud)
         with open(os.path.join(out, "rank%d.json" % rank), "w") as f:
             json.dump(runs, f)

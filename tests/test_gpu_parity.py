@@ -169,6 +169,9 @@ def test_resample_vs_oracle(orc, n, method):
     P[rng.integers(0, n, n // 7), d + 4] = 0.0         # zero-weight particles must never be selected
     P[:, d + 4] *= n / P[:, d + 4].sum()
     e = make_engine(dummy_spec(d), n, seed=99)
+    from tests import select_ref as sr
+
+    exact = sr.Cloud(P[:, d + 4])                       # the exact reference (tests/select_ref.py) next to the restatement
     for offsets in ("given", "philox"):
         e.upload_cloud(P)
         if offsets == "given":
@@ -176,9 +179,14 @@ def test_resample_vs_oracle(orc, n, method):
             anc = e.resample(method, stage=5, offsets=off)
             want = orc.resample(P[:, d + 4] / n, method, offsets=off)
         else:
+            off = orc.resample_offsets(method, n, seed=99, stage=5)
             anc = e.resample(method, stage=5)
             want = orc.resample(P[:, d + 4] / n, method, seed=99, stage=5)
         np.testing.assert_array_equal(anc, want)
+        ref = exact.select(method, n, off)
+        decided = ref["dist"] > sr.MARGIN_FLOOR
+        print(method, offsets, "undecided slots", int(np.count_nonzero(~decided)), "closest boundary", float(ref["dist"].min()))
+        np.testing.assert_array_equal(anc[decided], ref["anc"][decided])
         assert np.all(P[anc, d + 4] > 0)
         out = e.download_cloud()
         np.testing.assert_array_equal(out[:, :d + 4], P[anc, :d + 4])     # cloud.particles[new_inds, :]
