@@ -539,15 +539,23 @@ static double prior_logpdf(int fam, double a, double b, double x) {
     switch (fam) {
     case ORC_PRIOR_NORMAL: { double z = (x - a) / b; return -(z * z + LOG2PI) / 2.0 - log(b); }
     case ORC_PRIOR_UNIFORM: return (a <= x && x <= b) ? -log(b - a) : -INFINITY;
-    case ORC_PRIOR_GAMMA: return x < 0 ? -INFINITY : -lgamma(a) - a * log(b) + (a - 1.0) * log(x) - x / b;
+    /* edges as Distributions.jl has them (xlogy, xlog1py): a factor 0 times log 0 is 0 */
+    case ORC_PRIOR_GAMMA:
+        return x < 0 ? -INFINITY : -lgamma(a) - a * log(b) + (a == 1.0 ? 0.0 : (a - 1.0) * log(x)) - x / b;
     case ORC_PRIOR_BETA:
         return (x < 0 || x > 1) ? -INFINITY
-                                : (a - 1.0) * log(x) + (b - 1.0) * log1p(-x) - (lgamma(a) + lgamma(b) - lgamma(a + b));
+                                : (a == 1.0 ? 0.0 : (a - 1.0) * log(x)) + (b == 1.0 ? 0.0 : (b - 1.0) * log1p(-x)) -
+                                      (lgamma(a) + lgamma(b) - lgamma(a + b));
     case ORC_PRIOR_INVGAMMA: return x <= 0 ? -INFINITY : a * log(b) - lgamma(a) - (a + 1.0) * log(x) - b / x;
-    case ORC_PRIOR_ROOTINVGAMMA:
+    case ORC_PRIOR_ROOTINVGAMMA: {
+        /* log(x²) as the reference writes it while x² is a normal number; 2 log x where x² underflows or overflows */
+        const double x2 = x * x;
+        const int sq = x2 >= 2.2250738585072014e-308 && x2 <= 1.7976931348623157e308;
+        const double lx2 = sq ? log(x2) : 2.0 * log(x);
         return x <= 0 ? -INFINITY
-                      : log(2.0) - lgamma(a / 2.0) + (a / 2.0) * log(a * b * b / 2.0) - ((a + 1.0) / 2.0) * log(x * x) -
-                            a * b * b / (2.0 * x * x);
+                      : log(2.0) - lgamma(a / 2.0) + (a / 2.0) * log(a * b * b / 2.0) - ((a + 1.0) / 2.0) * lx2 -
+                            a * b * b / (2.0 * x2);
+    }
     default: return NAN;
     }
 }

@@ -35,11 +35,25 @@ __device__ inline double prior_logpdf(int fam, double a, double b, double k, dou
     switch (fam) {
     case SMCMI_PRIOR_NORMAL: { const double z = (x - a) / b; return -(z * z + LOG2PI) / 2.0 - k; }
     case SMCMI_PRIOR_UNIFORM: return (a <= x && x <= b) ? k : SMCMI_NEG_INF;
-    case SMCMI_PRIOR_GAMMA: return x < 0 ? SMCMI_NEG_INF : k + (a - 1.0) * log(x) - x / b;
-    case SMCMI_PRIOR_BETA: return (x < 0 || x > 1) ? SMCMI_NEG_INF : (a - 1.0) * log(x) + (b - 1.0) * log1p(-x) + k;
+    // Edges as Distributions.jl has them (xlogy, xlog1py): a factor 0 times log 0 is 0, so Gamma(1, .) at 0 and Beta(1, .) / Beta(., 1) at
+    // 0 / 1 are finite; a shape below 1 gives +Inf there and one above 1 -Inf by the product itself.
+    case SMCMI_PRIOR_GAMMA: {
+        const double t = (a == 1.0) ? 0.0 : (a - 1.0) * log(x);
+        return x < 0 ? SMCMI_NEG_INF : k + t - x / b;
+    }
+    case SMCMI_PRIOR_BETA: {
+        const double t0 = (a == 1.0) ? 0.0 : (a - 1.0) * log(x), t1 = (b == 1.0) ? 0.0 : (b - 1.0) * log1p(-x);
+        return (x < 0 || x > 1) ? SMCMI_NEG_INF : t0 + t1 + k;
+    }
     case SMCMI_PRIOR_INVGAMMA: return x <= 0 ? SMCMI_NEG_INF : k - (a + 1.0) * log(x) - b / x;
-    case SMCMI_PRIOR_ROOTINVGAMMA:
-        return x <= 0 ? SMCMI_NEG_INF : k - ((a + 1.0) / 2.0) * log(x * x) - a * b * b / (2.0 * x * x);
+    case SMCMI_PRIOR_ROOTINVGAMMA: {
+        // log(x²) as written while x² is a normal number (the same bits as before); where x² underflows or overflows, 2 log x - otherwise
+        // Inf - Inf = NaN below x = 1.5e-154 and -Inf in place of a finite value above 1.3e154
+        const double x2 = x * x;
+        const bool sq = x2 >= 2.2250738585072014e-308 && x2 <= 1.7976931348623157e308;
+        const double lx2 = (sq ? 1.0 : 2.0) * log(sq ? x2 : x);
+        return x <= 0 ? SMCMI_NEG_INF : k - ((a + 1.0) / 2.0) * lx2 - a * b * b / (2.0 * x2);
+    }
     default: return NAN;
     }
 }

@@ -134,6 +134,16 @@ def join_cloud(filename, n_pieces, save_cloud_file=True):
 
 # ---- priors on the host: densities as Distributions.jl / ModelConstructors define them, draws for Normal / Uniform on the build's
 # ---- counter-based RNG contract and numpy's Philox for the other families
+def _xlogy(c, y):
+    """c log y with Distributions.jl's edge rule (xlogy, xlog1py): a factor 0 times log 0 is 0; log 0 = -Inf"""
+    return 0.0 if c == 0.0 else (c * math.log(y) if y > 0.0 else -c * math.inf)
+
+
+def _over(p, q):
+    """p / q for p > 0, q >= 0 the way IEEE divides: Inf at q = 0"""
+    return p / q if q > 0.0 else math.inf
+
+
 def prior_logpdf(prior, x):
     fam, a, b = prior.triple()
     if fam == "normal":
@@ -142,15 +152,22 @@ def prior_logpdf(prior, x):
     if fam == "uniform":
         return -math.log(b - a) if a <= x <= b else -math.inf
     if fam == "gamma":                      # shape a, scale b
-        return -math.inf if x < 0 else -math.lgamma(a) - a * math.log(b) + (a - 1.0) * math.log(x) - x / b
+        return -math.inf if x < 0 else -math.lgamma(a) - a * math.log(b) + _xlogy(a - 1.0, x) - x / b
     if fam == "beta":
-        return -math.inf if (x < 0 or x > 1) else ((a - 1.0) * math.log(x) + (b - 1.0) * math.log1p(-x) -
-                                                   (math.lgamma(a) + math.lgamma(b) - math.lgamma(a + b)))
+        if x < 0 or x > 1:
+            return -math.inf
+        t1 = 0.0 if b == 1.0 else ((b - 1.0) * math.log1p(-x) if x < 1.0 else -(b - 1.0) * math.inf)
+        return _xlogy(a - 1.0, x) + t1 - (math.lgamma(a) + math.lgamma(b) - math.lgamma(a + b))
     if fam == "invgamma":                   # shape a, scale b
-        return -math.inf if x <= 0 else a * math.log(b) - math.lgamma(a) - (a + 1.0) * math.log(x) - b / x
+        return -math.inf if x <= 0 else a * math.log(b) - math.lgamma(a) - (a + 1.0) * math.log(x) - _over(b, x)
     if fam == "rootinvgamma":               # ν = a, τ = b
-        return -math.inf if x <= 0 else (math.log(2.0) - math.lgamma(a / 2.0) + (a / 2.0) * math.log(a * b * b / 2.0) -
-                                         ((a + 1.0) / 2.0) * math.log(x * x) - a * b * b / (2.0 * x * x))
+        if x <= 0:
+            return -math.inf
+        # log(x²) as ModelConstructors writes it while x² is a normal number; 2 log x where x² underflows or overflows
+        x2 = x * x
+        lx2 = math.log(x2) if 2.2250738585072014e-308 <= x2 <= 1.7976931348623157e308 else 2.0 * math.log(x)
+        return (math.log(2.0) - math.lgamma(a / 2.0) + (a / 2.0) * math.log(a * b * b / 2.0) - ((a + 1.0) / 2.0) * lx2 -
+                _over(a * b * b, 2.0 * x2))
     raise ValueError("unknown prior family %r" % (fam,))
 
 
