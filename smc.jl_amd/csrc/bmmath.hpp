@@ -14,6 +14,10 @@
 // on 2·10⁷ arguments incl. the end points (tests/bmmath_check.c, which includes THIS file with the estimates emulated at 2^-22):
 // -2 log <= 0.81 ulp, sqrt correctly rounded in every case, sin / cos <= 1.07 ulp.  In the mutation kernel: 104 VALU instructions per
 // pair instead of 160 (the polynomial coefficients as scalar operands).
+// On the hardware (MI355X: its own rcp / rsq / frexp; tests/test_gpu_mutation_range.py against the exact normals of tests/mutation_ref.py,
+// 1.0e6 normals through the generic body and the register kernel, ids on both sides of 2^32, stages up to 2^32 - 1, the smallest and the
+// largest ua and the ub nearest every quadrant boundary of 2^26 ids): the worst normal is 2.49 ulp from the exact one, 64 % are the
+// correctly rounded one; the test's bar is 3 ulp.
 // A normal differs from the libm-based oracle's in the last place or two - as it did with the device library - which moves a
 // Metropolis decision only when the uniform lies within ~1e-15 of the acceptance ratio (tests/test_gpu_strict.py counts flips).
 #pragma once

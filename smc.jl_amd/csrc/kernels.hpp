@@ -2498,9 +2498,9 @@ template <int D, class PD, class PI>
 struct MixDenseT {
     PD LsT, WsT;                  // [D*D] each
     PD mu_p, sdd_p, isd_p;        // [D]
-    PD sc;                        // [0] = ind_c, [1] = cst
+    PD sc;                        // [0] = ind_c, [1] = cst, [2] = the ssq below which ind_c * exp(-ssq / 2) is the reference's running product
     PI pos;                       // [D] position of parameter k in the block, or -1
-    static constexpr int DOUBLES = 2 * D * D + 3 * D + 2;
+    static constexpr int DOUBLES = 2 * D * D + 3 * D + 3;
     __device__ MixDenseT(PD buf, PI ibuf) : LsT(buf), WsT(buf + D * D), mu_p(buf + 2 * D * D), sdd_p(mu_p + D), isd_p(sdd_p + D), sc(isd_p + D), pos(ibuf) {}
 };
 template <int D> using MixDense = MixDenseT<D, double *, int *>;          // LDS / global memory, writable (mix_expand)
@@ -2558,10 +2558,17 @@ __device__ inline void mix_expand(const MixDense<D> &M, const double *Lb, const 
         M.isd_p[k] = pk >= 0 ? 1.0 / sdn_b[pk] : 0.0;
     }
     if (tid == 0) {
-        double ic = 1.0;
-        for (int e = 0; e < db; ++e) ic = ic / (sdn_b[e] * sqrt(2.0 * M_PI));     // the reference's running product (helpers.jl:150-154)
+        double ic = 1.0, ic_max = 1.0, ic_min = 1.0;
+        for (int e = 0; e < db; ++e) {
+            ic = ic / (sdn_b[e] * sqrt(2.0 * M_PI));     // the reference's running product (helpers.jl:150-154)
+            ic_max = fmax(ic_max, ic); ic_min = fmin(ic_min, ic);
+        }
         M.sc[0] = ic;
         M.sc[1] = (double)db * LOG2PI + logdet;
+        // The reference interleaves the quotients with the exponentials exp(-z_i² / 2): its intermediates lie between ic_min exp(-ssq / 2) and
+        // ic_max.  While all of them are normal numbers the one product ind_c * exp(-ssq / 2) is that running product up to rounding; beyond
+        // (and for a NaN scale: every comparison false) mix_densities forms it coordinate by coordinate, as the reference does.
+        M.sc[2] = (ic_max < 1e300 && ic_min > 1e-300) ? 2.0 * (log(ic_min) + 700.0) : -1.0;
     }
     __syncthreads();
 }
@@ -2602,7 +2609,28 @@ SMCMI_FP_CONTRACT
     mix_solve_rows<D, 0, HALF, MX>(M, x, xn, quad, quad_s, quad_d);
     mix_solve_rows<D, HALF, D, MX>(M, x, xn, quad, quad_s, quad_d);
     const double cst = M.sc[1];
-    const double common = c_alpha * exp(-(cst + quad) / 2.0) + (1.0 - c_alpha) / 2.0 * (M.sc[0] * exp(-0.5 * ssq));
+    double ind;
+    if (__builtin_expect(ssq < M.sc[2], 1)) ind = M.sc[0] * exp(-0.5 * ssq);
+    else {
+        // the reference's own order (block order, quotient then exponential: helpers.jl:145-149) where an intermediate of it may leave the
+        // normal range: what overflows or vanishes on the way stays +Inf or 0 there, and must here
+        ind = 1.0;
+#pragma nounroll
+        for (int e = 0; e < D; ++e) {
+            double zz = 0.0, isd = 0.0;
+            bool found = false;                            // (block positions beyond d_b hold no parameter)
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                const bool here = M.pos[k] == e;
+                zz = here ? (x[k] - xn[k]) * M.isd_p[k] : zz;
+                isd = here ? M.isd_p[k] : isd;
+                found = found || here;
+            }
+            // (the block keeps 1 / sd: 1 / (1 / sd) is sd to an ulp, and a scale of +Inf - 1 / sd = 0 - divides by +Inf as the reference does)
+            if (found) ind = ind / ((1.0 / isd) * sqrt(2.0 * M_PI)) * exp(-0.5 * zz * zz);
+        }
+    }
+    const double common = c_alpha * exp(-(cst + quad) / 2.0) + (1.0 - c_alpha) / 2.0 * ind;
     q0 = common + (1.0 - c_alpha) / 2.0 * exp(-(cst + quad_s) / 2.0);
     q1 = common + (1.0 - c_alpha) / 2.0 * exp(-(cst + quad_d) / 2.0);
 }
@@ -2755,8 +2783,10 @@ SMCMI_FP_CONTRACT
     for (int e = 0; e < D; ++e) zz2 += z[e] * z[e];
     if constexpr (ALPHA1) {
         // q0 = q1 = log N(θ_b; ϑ_b, c²Σ) bit for bit (sign-symmetric quadratic form), other mixture terms have weight 0:
-        // q0 - q1 == 0 unless exp() underflows to 0 (log-density < -745.13: the reference gets NaN and rejects).
-        q1 = (-((double)db * LOG2PI + logdet_b + zz2) / 2.0 < -745.1332191019412) ? __builtin_nan("") : 0.0;
+        // q0 - q1 == 0 unless exp() underflows to 0 (log-density < -745.13: the reference gets NaN and rejects) or overflows (> 709.78: both
+        // densities are +Inf, the reference sets q0 = 0 and rejects with q0 - q1 = -Inf).
+        const double lp_sym = -((double)db * LOG2PI + logdet_b + zz2) / 2.0;
+        q1 = (lp_sym < -745.1332191019412 || lp_sym > 709.782712893384) ? __builtin_nan("") : 0.0;
         ph.template at<5>();
         // column sweep: D independent accumulators (one per parameter), one factor column live at a time; every
         // accumulator still adds its terms in ascending e, i.e. the same order as the row-wise triangular product

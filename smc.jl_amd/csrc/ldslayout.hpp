@@ -236,7 +236,7 @@ constexpr Layout<X_N> ens(int D, long long n) {
 // D + 5 columns a block outgrows a CU's 160 KB beyond n_para 7.  K3_STATIC_REST: a bound on the rest of the kernel's static arrays,
 // which tests/test_abi_cpu.py holds against the compiler's report.
 constexpr size_t CU_LDS_BYTES = 160 * 1024, K3_STATIC_REST = 24 * 1024;
-constexpr size_t k3_mix_static_bytes(int D) { return ((size_t)T3 * D + 3 * D * D + 3 * D + 2) * sizeof(double); }
+constexpr size_t k3_mix_static_bytes(int D) { return ((size_t)T3 * D + 3 * D * D + 3 * D + 3) * sizeof(double); }     // (T3 D z columns; MixDense<D>::DOUBLES + D D)
 constexpr int k3_sel_cols(int D, bool alpha1) {
     return (alpha1 || K3_STATIC_REST + k3_mix_static_bytes(D) + lds::seg3(D, D + 5).bytes <= CU_LDS_BYTES) ? D + 5 : 0;
 }
