@@ -32,7 +32,7 @@ extern "C" {
 
 enum { SMCMI_OK = 0, SMCMI_ERR_ARG = -1, SMCMI_ERR_HIP = -2, SMCMI_ERR_NAN_ESS = -3, SMCMI_ERR_POSDEF = -4,
        SMCMI_ERR_CAPACITY = -5, SMCMI_ERR_BRACKET = -6, SMCMI_ERR_UNSUPPORTED = -7, SMCMI_ERR_STATE = -8,
-       SMCMI_ERR_CALLBACK = -9, SMCMI_ERR_TIMEOUT = -10 };
+       SMCMI_ERR_CALLBACK = -9, SMCMI_ERR_TIMEOUT = -10, SMCMI_ERR_COMPILE = -11 };
 
 /* prior families: Distributions.jl / ModelConstructors priors reachable from `prior(parameters)` (src/mutation.jl:95) */
 enum { SMCMI_PRIOR_NORMAL = 0, SMCMI_PRIOR_UNIFORM = 1, SMCMI_PRIOR_GAMMA = 2, SMCMI_PRIOR_BETA = 3,
@@ -195,6 +195,44 @@ typedef struct {
     void *user_data;
 } smcmi_device_likelihood;
 int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const smcmi_device_likelihood *lik);
+
+/* ---- user likelihood as HIP SOURCE, compiled by the library at run time and called from a kernel of the engine's own: the closure on
+   the GPU for callers without a toolchain (Python, Julia, plain C).  The source defines ONE function,
+
+       __device__ double loglik(const double *theta, long long ld, int d, const double *data, long long rows, long long cols,
+                                const double *par, long long n_par);
+
+   theta[j * ld] is parameter j (j < d) of this proposal; data (rows x cols, column-major) and par (n_par) are the engine's device copies
+   of what smcmi_set_likelihood_program was given (NULL when it was given none).  It returns the log-likelihood; -Inf is allowed, NaN is
+   taken as -Inf.  Contract: a pure function of its arguments; called by one thread per in-bounds proposal, in no particular order; it
+   must not synchronise the workgroup, must not write through its pointers, and the source must not #include files of the user's own.
+   smcmi_program_compile needs no GPU and no handle.  It compiles the source followed by the engine's wrapper kernel for gfx950 with
+   -O3 -ffp-contract=off -std=c++17 plus `options` (NULL, or extra compiler options separated by white space, e.g. "-DT=40"); an option
+   that names a target (offload-arch, mcpu, mxnack) or contains "xnack" is refused with SMCMI_ERR_ARG, like an entry that is not a C
+   identifier of at most 64 characters or a NULL source.  entry = NULL means "loglik".  A compiler error - and a source without the entry
+   function, which the wrapper then fails to compile against - gives SMCMI_ERR_COMPILE with *out still set: smcmi_program_log has the
+   compiler's messages, with the line numbers of the user's source under the file name likelihood.hip, and the caller destroys the program.
+   No run-time compiler on this machine (libhiprtc is opened on first use): SMCMI_ERR_UNSUPPORTED.
+   smcmi_program_log: "" when clean; valid until smcmi_program_destroy.  smcmi_program_code: the gfx950 code object, for callers that cache
+   (SMCMI_ERR_ARG for a program that did not compile).
+   smcmi_set_likelihood_program loads the code object on the handle's device, copies data and par (host pointers; either may be NULL / 0)
+   and registers the program at `which`; p = NULL unregisters.  Registering replaces a device family, a host callback or a device callback
+   at `which`, and the other way round.  A program that did not compile: SMCMI_ERR_ARG, the handle's previous likelihood stays.  The handle
+   keeps its own module: the program may be destroyed right after the call and registered on any number of handles and devices.
+   A program is served wherever a device callback is (smcmi_run, smcmi_run_group, smcmi_init_from_prior, smcmi_initialize_likelihoods,
+   smcmi_eval_cloud_callback, tempered updates through which = SMCMI_WHICH_OLD, pause / continue), refused where one is (smcmi_run_sharded,
+   smcmi_run_ensemble: SMCMI_ERR_UNSUPPORTED), and a host callback on the other vintage gives SMCMI_ERR_STATE from the run; a device
+   callback on the other vintage is fine.  One launch per score: bounds gate (out-of-bounds proposals never reach the function), NaN -> -Inf
+   and the evaluation count happen inside it, and the host reads nothing per MH step.  smcmi_callback_stats: calls = launches,
+   evaluations = rows the function scored.  smcmi_callback_phases: `inside the callback` and the count wait are 0, the launches are under
+   `enqueueing`. */
+typedef struct smcmi_program smcmi_program;
+int smcmi_program_compile(const char *source, const char *entry, const char *options, smcmi_program **out);
+const char *smcmi_program_log(const smcmi_program *p);
+int smcmi_program_code(const smcmi_program *p, const void **code, int64_t *size);
+int smcmi_program_destroy(smcmi_program *p);
+int smcmi_set_likelihood_program(smcmi_handle *h, int32_t which, const smcmi_program *p, const double *data, int64_t rows, int64_t cols,
+                                 const double *par, int64_t n_par);
 
 /* ---- cloud transfer (cloud.particles; get_vals/get_loglh/... read columns of the download) ---- */
 int smcmi_upload_cloud(smcmi_handle *h, const double *particles);       /* n_local x R, column-major */

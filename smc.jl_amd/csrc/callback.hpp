@@ -71,7 +71,7 @@ static inline double cb_now_ms() { return std::chrono::duration<double, std::mil
 static int ensure_split_buffers(smcmi_handle *h);
 #include "devcallback.hpp"
 // the phase clocks of the handle's kind of closure
-static inline double *cb_phase_ms(smcmi_handle *h) { return h->dcb[0] ? h->dcbuf->phase_ms : h->cbuf->phase_ms; }
+static inline double *cb_phase_ms(smcmi_handle *h) { return device_lik(h) ? h->dcbuf->phase_ms : h->cbuf->phase_ms; }
 
 // Evaluate callback `which` on the m_rows x d column-major block `theta` (leading dimension m_rows) for the rows whose `gate` is finite
 // (gate = the proposals' log-priors: -Inf = the bounds check failed, the reference never calls the likelihood there, mutation.jl:93);
@@ -153,7 +153,7 @@ static int host_propose_enqueue(smcmi_handle *h, int step, int blk) {
     return 0;
 }
 static int host_mutation(smcmi_handle *h, const smcmi_run_config *rc, bool tempered, bool first_enqueued = false) {
-    if (h->dcb[0]) return device_mutation(h, rc, tempered);         // the likelihood is a device function: nothing crosses PCIe (devcallback.hpp)
+    if (device_lik(h)) return device_mutation(h, rc, tempered);     // the likelihood is a device function or a program: nothing crosses PCIe (devcallback.hpp)
     CallbackBuffers *b = h->cbuf;
     const long long n = h->n;
     const int d = h->d;
@@ -197,7 +197,7 @@ static int host_mutation(smcmi_handle *h, const smcmi_run_config *rc, bool tempe
 // loglh (and old_loglh) columns of the handle's cloud from the callbacks: initial clouds whose parameter columns were uploaded
 // without likelihood values (`smcmi_eval_cloud_callback`), and initialize_likelihoods! (src/initialization.jl:153-186)
 static int callback_fill_loglh(smcmi_handle *h, int which, int column) {
-    if (h->dcb[which]) return device_fill_loglh(h, which, column);
+    if (device_lik(h, which)) return device_fill_loglh(h, which, column);
     if (int e = ensure_callback_buffers(h)) return e;
     CallbackBuffers *b = h->cbuf;
     const long long n = h->n;
@@ -215,7 +215,7 @@ static int callback_fill_loglh(smcmi_handle *h, int which, int column) {
 // (attempt a of particle i = the draws k_init_prior makes on its a-th outer attempt), the callback scores them, particles without
 // a finite log-likelihood are redrawn (one_draw's loop, :23-63) - the cloud a device family with the same values would start from.
 static int callback_init_from_prior(smcmi_handle *h) {
-    if (h->dcb[0]) return device_init_from_prior(h);
+    if (device_lik(h)) return device_init_from_prior(h);
     // (the Gamma-family draws keep their acceptance uniforms in tag k | 64: beyond 64 parameters that collides with parameter k's normal)
     if (h->d > 64) return set_err(SMCMI_ERR_UNSUPPORTED, "device prior draws serve n_para <= 64");
     if (int e = ensure_callback_buffers(h)) return e;
@@ -256,7 +256,7 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     if (int e = check_run_config(h, rc)) return e;
     const bool adaptive = !rc->use_fixed_schedule;
     const bool tempered = closure_lik(h, 1);
-    const bool on_device = h->dcb[0] != nullptr;          // the likelihood is a device function (devcallback.hpp): no staging buffers, no copy streams
+    const bool on_device = device_lik(h);                 // the likelihood is a device function or a program (devcallback.hpp): no staging buffers, no copy streams
     if (int e = on_device ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e;
     if (pull_state(h)) return SMCMI_ERR_HIP;
     const std::vector<double> sched = make_schedule(rc);
@@ -277,6 +277,7 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     const auto t0 = std::chrono::steady_clock::now();
     const int max_iter = (adaptive ? h->cfg.max_stages : rc->n_phi - 1) - base;
     h->cb_calls = 0; h->cb_evals = 0;
+    if (int e = prog_reset(h)) return e;
     double *phase_ms = cb_phase_ms(h);
     for (int k = 0; k < CBP_N; ++k) phase_ms[k] = 0.0;
     const StageRun run{adaptive, rc->resampling_method, rc->n_blocks, rc->alpha, acc_nb};
@@ -330,6 +331,7 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     if (!on_device) HIP_TRY(hipStreamSynchronize(h->cbuf->s_down));  // (a proposal enqueued for a stage that turned out to be the end of the run)
     if (pull_state(h)) return SMCMI_ERR_HIP;
     const auto t1 = std::chrono::steady_clock::now();
+    if (int e = prog_collect(h)) return e;              // (a program's evaluation count: the run's one read of it)
     res->kernel_ms_mutate = 0.0; res->n_mutate_launches = 0;
     finish_result(res, s, t0, t1);
     h->last_n_stages = s.stage;

@@ -128,6 +128,8 @@ static __global__ void __launch_bounds__(TB) k_dcb_init_advance(int *__restrict_
 // Score the rows of the n x d column-major block `theta` (device, leading dimension n) whose `gate` is not -Inf with device callback `which`,
 // results into `lik_out` (device, n; -Inf for the others): count -> [pack] -> the user's function -> scatter, all on the handle's stream.
 // reuse_count: the gate is the one of the call before (the old-data callback of a tempered update) - its count and pack are still valid.
+// A compiled program at `which` (program.hpp) is called from a kernel of the engine's own, so bounds gate, NaN -> -Inf and the evaluation count
+// are that one launch: no count, no pack, no scatter, and nothing the host waits for (reuse_count is moot).
 static int eval_device_callback(smcmi_handle *h, int which, const double *theta, const double *gate, double *lik_out, bool reuse_count = false) {
     DevCallbackBuffers *b = h->dcbuf;
     const long long n = h->n;
@@ -135,6 +137,15 @@ static int eval_device_callback(smcmi_handle *h, int which, const double *theta,
     const unsigned nb = (unsigned)((n + TB - 1) / TB);
     hipStream_t s = h->stream;
     double t0 = cb_now_ms();
+    if (h->prog[which].kernel) {
+        const program::Args a{theta, gate, n, n, d, h->d_prog_data[which], h->prog_rows[which], h->prog_cols[which],
+                              h->d_prog_par[which], h->prog_npar[which], lik_out, h->d_prog_evals};
+        const hipError_t e = (hipError_t)program::launch(h->prog[which], a, (void *)s);
+        b->phase_ms[CBP_ENQUEUE] += cb_now_ms() - t0;
+        if (e != hipSuccess) return set_err(SMCMI_ERR_HIP, std::string("launching the compiled likelihood: ") + hipGetErrorString(e));
+        h->cb_calls += 1;
+        return 0;
+    }
     if (!reuse_count) {
         k_dcb_count<<<nb, TB, 0, s>>>(gate, n, b->d_blk);
         k_dcb_scan<<<1, DCB_ST, 0, s>>>(b->d_blk, (long long)nb, b->d_cnt);
@@ -168,6 +179,23 @@ static int eval_device_callback(smcmi_handle *h, int which, const double *theta,
     return 0;
 }
 
+// The rows the program launches scored since the last collect, from the device's counter into cb_evals: once per run or stand-alone call
+// (the stream is drained here; every caller is about to wait for it anyway).  prog_reset: the counter starts a run at 0.
+static inline bool has_program(const smcmi_handle *h) { return h->prog[0].kernel != nullptr || h->prog[1].kernel != nullptr; }
+static int prog_reset(smcmi_handle *h) {
+    if (has_program(h)) HIP_TRY(hipMemsetAsync(h->d_prog_evals, 0, sizeof(unsigned long long) * program::EVAL_WORDS, h->stream));
+    return 0;
+}
+static int prog_collect(smcmi_handle *h) {
+    if (!has_program(h)) return 0;
+    std::vector<unsigned long long> c((size_t)program::EVAL_WORDS, 0ull);
+    HIP_TRY(hipMemcpyAsync(c.data(), h->d_prog_evals, sizeof(unsigned long long) * program::EVAL_WORDS, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_prog_evals, 0, sizeof(unsigned long long) * program::EVAL_WORDS, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < program::EVAL_SLOTS; ++k) h->cb_evals += (long long)c[(size_t)k * program::EVAL_STRIDE];
+    return 0;
+}
+
 // host_mutation for a device callback: per MH step x block propose (k_mutate<1>, plain n x d proposals + their log-priors) -> the user's
 // function on the in-bounds ones (new data, and old data in a tempered update) -> accept (k_mutate<2>), in stream order on h->stream.
 static int device_mutation(smcmi_handle *h, const smcmi_run_config *rc, bool tempered) {
@@ -183,7 +211,8 @@ static int device_mutation(smcmi_handle *h, const smcmi_run_config *rc, bool tem
             k_mutate<1><<<h->nb_mut, h->mut_T, h->mut_lds, h->stream>>>(h->cl, h->d_st, h->d_model, ma, h->d_acc_part, 0);
             h->dcbuf->phase_ms[CBP_ENQUEUE] += cb_now_ms() - t0;
             if (int e = eval_device_callback(h, 0, h->d_prop, h->d_prop_lp, h->d_lik_new)) return e;
-            if (tempered) { if (int e = eval_device_callback(h, 1, h->d_prop, h->d_prop_lp, h->d_lik_old, true)) return e; }
+            // (the old-data callback reuses the count and pack of the new-data callback - unless that one was a program, which made neither)
+            if (tempered) { if (int e = eval_device_callback(h, 1, h->d_prop, h->d_prop_lp, h->d_lik_old, h->prog[0].kernel == nullptr)) return e; }
             t0 = cb_now_ms();
             ma.lik_new = h->d_lik_new; ma.lik_old_new = tempered ? h->d_lik_old : nullptr;
             ma.last = (step == rc->n_mh_steps - 1 && blk == rc->n_blocks - 1) ? 1 : 0;
@@ -201,7 +230,7 @@ static int device_fill_loglh(smcmi_handle *h, int which, int column) {
     double *c0 = h->cl.buf[0];
     if (int e = eval_device_callback(h, which, c0, c0 + (long long)(h->d + 1) * n, c0 + (long long)column * n)) return e;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
+    return prog_collect(h);
 }
 
 // callback_init_from_prior for a device callback: the same draws (k_draw_prior, same attempt numbering), the same redraw loop, with the
@@ -232,5 +261,5 @@ static int device_init_from_prior(smcmi_handle *h) {
     }
     HIP_TRY(hipMemcpyAsync(h->cl.buf[0] + (long long)d * n, lik, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
+    return prog_collect(h);
 }

@@ -16,6 +16,7 @@
 
 #include "../../include/smcmi.h"
 #include "devmem.hpp"
+#include "program.hpp"
 #include "devstate.hpp"
 #include "kernels.hpp"
 #include "stage2.hpp"
@@ -155,7 +156,15 @@ struct smcmi_handle {
     smcmi_lik_device_fn dcb[2] = {nullptr, nullptr};
     void *dcb_ud[2] = {nullptr, nullptr};
     DevCallbackBuffers *dcbuf = nullptr;
+    // user likelihoods compiled at run time from HIP source (program.hpp): the handle's own module, its device copies of the user's data and
+    // parameters, and the 64-bit count of rows the wrapper kernel scored (read by the host once per run or stand-alone call, prog_collect)
+    program::Loaded prog[2];
+    double *d_prog_data[2] = {nullptr, nullptr}, *d_prog_par[2] = {nullptr, nullptr};
+    long long prog_rows[2] = {0, 0}, prog_cols[2] = {0, 0}, prog_npar[2] = {0, 0};
+    unsigned long long *d_prog_evals = nullptr;
     devmem::Owner<> mem;           // every device / pinned buffer above is this owner's (devmem.hpp); e2, cbuf and dcbuf hold their own
 };
-// is likelihood `which` of the handle a user closure - a host callback or a device callback?  (which = 0: "this is a closure run")
-static inline bool closure_lik(const smcmi_handle *h, int which = 0) { return h->cb[which] != nullptr || h->dcb[which] != nullptr; }
+// is likelihood `which` evaluated on the handle's stream from device pointers - a device callback or a compiled program?
+static inline bool device_lik(const smcmi_handle *h, int which = 0) { return h->dcb[which] != nullptr || h->prog[which].kernel != nullptr; }
+// is likelihood `which` of the handle a user closure - a host callback, a device callback or a program?  (which = 0: "this is a closure run")
+static inline bool closure_lik(const smcmi_handle *h, int which = 0) { return h->cb[which] != nullptr || device_lik(h, which); }

@@ -1,0 +1,150 @@
+// program.hip - likelihoods given as HIP source (include/smcmi.h smcmi_program_*): compile at run time, load on a handle's device, launch.
+// A translation unit of its own, like summary.hip: nothing the engines' units compile depends on it, and it holds no kernel - the device
+// code is the text of csrc/progsrc.hpp, compiled together with the user's function by the run-time compiler.
+// libhiprtc is dlopen'ed the way sharded.hpp opens RCCL (hand-declared prototypes): libsmcmi.so has no link-time dependency on it, and a
+// machine without it gets SMCMI_ERR_UNSUPPORTED from smcmi_program_compile and loses nothing else.
+#include <hip/hip_runtime.h>
+
+#include <dlfcn.h>
+
+#include <mutex>
+
+#include "../../include/smcmi.h"
+#include "program.hpp"
+#include "progsrc.hpp"
+
+static_assert(program::EVAL_SLOTS == progsrc::EVAL_SLOTS && program::EVAL_STRIDE == progsrc::EVAL_STRIDE, "the wrapper text and the host disagree about the counter");
+
+namespace {
+
+// the eight entry points of the run-time compiler this unit uses (hiprtc.h: hiprtcResult is an enum, 0 = success; hiprtcProgram a pointer)
+typedef void *rtc_prog;
+struct Rtc {
+    void *lib = nullptr;
+    bool tried = false;
+    std::string why;
+    int (*CreateProgram)(rtc_prog *, const char *src, const char *name, int n_headers, const char **headers, const char **include_names) = nullptr;
+    int (*CompileProgram)(rtc_prog, int n_options, const char **options) = nullptr;
+    int (*GetProgramLogSize)(rtc_prog, size_t *) = nullptr;
+    int (*GetProgramLog)(rtc_prog, char *) = nullptr;
+    int (*GetCodeSize)(rtc_prog, size_t *) = nullptr;
+    int (*GetCode)(rtc_prog, char *) = nullptr;
+    int (*DestroyProgram)(rtc_prog *) = nullptr;
+    const char *(*GetErrorString)(int) = nullptr;
+};
+Rtc g_rtc;
+std::mutex g_rtc_mutex;
+
+bool rtc_open(std::string *err) {
+    std::lock_guard<std::mutex> lock(g_rtc_mutex);
+    if (!g_rtc.tried) {
+        g_rtc.tried = true;
+        for (const char *c : {"libhiprtc.so", "libhiprtc.so.7"}) {
+            g_rtc.lib = dlopen(c, RTLD_NOW | RTLD_LOCAL);
+            if (g_rtc.lib) break;
+        }
+        if (!g_rtc.lib) {
+            const char *e = dlerror();
+            g_rtc.why = std::string("cannot load the run-time compiler (libhiprtc): ") + (e ? e : "not found");
+        } else {
+#define SMCMI_RTC_SYM(field) *(void **)(&g_rtc.field) = dlsym(g_rtc.lib, "hiprtc" #field)
+            SMCMI_RTC_SYM(CreateProgram); SMCMI_RTC_SYM(CompileProgram); SMCMI_RTC_SYM(GetProgramLogSize); SMCMI_RTC_SYM(GetProgramLog);
+            SMCMI_RTC_SYM(GetCodeSize); SMCMI_RTC_SYM(GetCode); SMCMI_RTC_SYM(DestroyProgram); SMCMI_RTC_SYM(GetErrorString);
+#undef SMCMI_RTC_SYM
+            if (!g_rtc.CreateProgram || !g_rtc.CompileProgram || !g_rtc.GetProgramLogSize || !g_rtc.GetProgramLog || !g_rtc.GetCodeSize ||
+                !g_rtc.GetCode || !g_rtc.DestroyProgram) {
+                g_rtc.why = "libhiprtc lacks an entry point of the run-time compiler";
+                dlclose(g_rtc.lib);
+                g_rtc.lib = nullptr;
+            }
+        }
+    }
+    if (!g_rtc.lib && err) *err = g_rtc.why;
+    return g_rtc.lib != nullptr;
+}
+std::string rtc_text(int code) {
+    const char *s = g_rtc.GetErrorString ? g_rtc.GetErrorString(code) : nullptr;
+    return s ? std::string(s) : "hiprtc error " + std::to_string(code);
+}
+
+}      // namespace
+
+namespace program {
+
+int compile(const char *source, const char *entry, const char *options, smcmi_program **out, std::string *err) {
+    if (out) *out = nullptr;
+    if (!source || !out) { *err = "smcmi_program_compile: null argument"; return SMCMI_ERR_ARG; }
+    const char *ent = entry ? entry : progsrc::DEFAULT_ENTRY;
+    if (!progsrc::valid_entry(ent)) { *err = "smcmi_program_compile: the entry is not a C identifier of at most 64 characters"; return SMCMI_ERR_ARG; }
+    std::vector<std::string> extra;
+    if (!progsrc::split_options(options, &extra, err)) return SMCMI_ERR_ARG;
+    if (!rtc_open(err)) return SMCMI_ERR_UNSUPPORTED;
+    std::vector<std::string> opts = progsrc::base_options();
+    opts.insert(opts.end(), extra.begin(), extra.end());
+    std::vector<const char *> optv;
+    for (const std::string &o : opts) optv.push_back(o.c_str());
+    const progsrc::Assembled text = progsrc::assemble(source, ent);
+
+    rtc_prog prog = nullptr;
+    int rc = g_rtc.CreateProgram(&prog, text.text.c_str(), progsrc::USER_FILE, 0, nullptr, nullptr);
+    if (rc != 0 || !prog) { *err = "hiprtcCreateProgram: " + rtc_text(rc); return SMCMI_ERR_HIP; }
+    smcmi_program *p = new smcmi_program();
+    p->entry = ent;
+    rc = g_rtc.CompileProgram(prog, (int)optv.size(), optv.data());
+    size_t len = 0;
+    if (g_rtc.GetProgramLogSize(prog, &len) == 0 && len > 1) {
+        std::vector<char> buf(len + 1, '\0');
+        if (g_rtc.GetProgramLog(prog, buf.data()) == 0) p->log = buf.data();
+    }
+    if (rc == 0) {
+        size_t size = 0;
+        rc = g_rtc.GetCodeSize(prog, &size);
+        if (rc == 0 && size > 0) {
+            p->code.resize(size);
+            rc = g_rtc.GetCode(prog, p->code.data());
+        }
+        p->ok = rc == 0 && size > 0;
+        if (!p->ok && p->log.empty()) p->log = "the run-time compiler returned no code object: " + rtc_text(rc);
+    } else if (p->log.empty()) p->log = rtc_text(rc);
+    g_rtc.DestroyProgram(&prog);
+    *out = p;
+    if (!p->ok) {
+        p->code.clear();
+        *err = "the likelihood source did not compile (entry '" + p->entry + "'); smcmi_program_log has the compiler's messages";
+        return SMCMI_ERR_COMPILE;
+    }
+    return SMCMI_OK;
+}
+
+int load(const smcmi_program *p, Loaded *out, std::string *err) {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    hipError_t e = hipModuleLoadData(&mod, p->code.data());
+    if (e == hipSuccess) e = hipModuleGetFunction(&fn, mod, progsrc::KERNEL_NAME);
+    if (e != hipSuccess) {
+        *err = std::string("loading the compiled likelihood: ") + hipGetErrorString(e);
+        if (mod) (void)hipModuleUnload(mod);
+        (void)hipGetLastError();
+        return SMCMI_ERR_HIP;
+    }
+    out->module = (void *)mod;
+    out->kernel = (void *)fn;
+    return SMCMI_OK;
+}
+void unload(Loaded *l) {
+    if (l->module) (void)hipModuleUnload((hipModule_t)l->module);
+    l->module = nullptr;
+    l->kernel = nullptr;
+}
+
+unsigned grid_for(long long n) {
+    const long long nb = (n + progsrc::BLOCK - 1) / progsrc::BLOCK;
+    return (unsigned)(nb < 1 ? 1 : nb > 2048 ? 2048 : nb);
+}
+int launch(const Loaded &l, const Args &a, void *stream) {
+    Args v = a;
+    void *args[] = {&v.theta, &v.gate, &v.n, &v.ld, &v.d, &v.data, &v.rows, &v.cols, &v.par, &v.n_par, &v.lik, &v.evals};
+    return (int)hipModuleLaunchKernel((hipFunction_t)l.kernel, grid_for(a.n), 1, 1, progsrc::BLOCK, 1, 1, 0, (hipStream_t)stream, args, nullptr);
+}
+
+}      // namespace program

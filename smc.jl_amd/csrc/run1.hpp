@@ -101,8 +101,8 @@ static int check_lik_pair(const smcmi_handle *h) {
     if ((closure_lik(h) && old_dev) || (!closure_lik(h) && old_cb))
         return set_err(SMCMI_ERR_UNSUPPORTED, "the new and the old likelihood must both be device families or both host callbacks");
     // (a host callback next to a device callback: one mutation would need both paths)
-    if ((h->cb[0] && h->dcb[1]) || (h->dcb[0] && h->cb[1]))
-        return set_err(SMCMI_ERR_STATE, "the new and the old likelihood must both be host callbacks or both device callbacks");
+    if ((h->cb[0] && device_lik(h, 1)) || (device_lik(h, 0) && h->cb[1]))
+        return set_err(SMCMI_ERR_STATE, "the new and the old likelihood must both be host callbacks or both device callbacks / programs");
     return 0;
 }
 // engine 1's run of one handle (smcmi_run sends it the runs that are neither closure runs nor engine 2's)

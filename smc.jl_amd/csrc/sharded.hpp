@@ -384,9 +384,9 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     // proposal set-up, the collectives - is this driver's.  The callback mutation leaves neither energy sums nor energy maxima, so
     // such runs walk the schedule without a predictor, unshifted, one stage per host sync (the closure needs the host anyway).
     // (a device callback - smcmi_set_likelihood_device - takes the same route: host_mutation branches on the kind)
-    const bool host_mut = closure_lik(h0), tempered_cb = closure_lik(h0, 1), dev_cb = h0->dcb[0] != nullptr;
+    const bool host_mut = closure_lik(h0), tempered_cb = closure_lik(h0, 1), dev_cb = device_lik(h0);
     for (auto *h : g.hs)
-        if (closure_lik(h) != host_mut || closure_lik(h, 1) != tempered_cb || (h->dcb[0] != nullptr) != dev_cb) return set_err(SMCMI_ERR_STATE, "every shard needs the same likelihood callbacks");
+        if (closure_lik(h) != host_mut || closure_lik(h, 1) != tempered_cb || device_lik(h) != dev_cb) return set_err(SMCMI_ERR_STATE, "every shard needs the same likelihood callbacks");
     const bool predict = adaptive && !sw().no_predictor && !host_mut;
     const int sel_mode = sw().no_select_predict;   // development only
     const bool predict_select = adaptive && can_fuse_post(h0) && sel_mode != 1 && !host_mut;
@@ -394,7 +394,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
     for (auto *h : g.hs) {
         HIP_TRY(hipSetDevice(h->cfg.device));
         if (ensure_shard_buffers(h) || pull_state(h) || upload_sched(h, sched.data(), rc->n_phi)) return SMCMI_ERR_HIP;
-        if (host_mut) { if (int e = dev_cb ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e; h->rng_ahead = false; h->cb_energy = false; h->cb_calls = 0; h->cb_evals = 0; }
+        if (host_mut) { if (int e = dev_cb ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e; h->rng_ahead = false; h->cb_energy = false; h->cb_calls = 0; h->cb_evals = 0; if (int e = prog_reset(h)) return e; }
         else if (int e = ensure_zbuf(h, rc->n_mh_steps, rc->n_blocks)) return e;
         // (a continuation: every shard keeps the loop scalars, records and history it holds - the same scalars on every shard)
         if (int e = start_state(h, rc, make_run_params(h, rc), false)) return e;
@@ -660,6 +660,7 @@ static int run_sharded_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_res
         HIP_TRY(hipSetDevice(h->cfg.device));
         k_stage_begin<<<1, BT, 0, h->stream>>>(h->d_st, h->d_sched, h->d_tot_acc + EACC, 1, h->rec);
         if (pull_state(h)) return SMCMI_ERR_HIP;
+        if (int e = prog_collect(h)) return e;
         h->last_n_stages = h->h_st.stage;
     }
     const auto t1 = std::chrono::steady_clock::now();

@@ -316,12 +316,23 @@ static void update_lik_prefix(smcmi_handle *h) {
     h->h_model.lik_prefix = ok ? (int)b.cols : 0;
 }
 
+// a compiled program registered at `which` (smcmi_set_likelihood_program) leaves the handle: its module is unloaded once the stream no longer
+// runs it, its copies of the user's data and parameters go back to the owner.  The handle's device is current.
+static void drop_program(smcmi_handle *h, int which) {
+    if (h->prog[which].module && h->stream) (void)hipStreamSynchronize(h->stream);
+    program::unload(&h->prog[which]);
+    h->mem.release(&h->d_prog_data[which]);
+    h->mem.release(&h->d_prog_par[which]);
+    h->prog_rows[which] = 0; h->prog_cols[which] = 0; h->prog_npar[which] = 0;
+}
+
 extern "C" int smcmi_set_likelihood(smcmi_handle *h, int32_t which, int32_t family, const double *par, int64_t n_par,
                                     const double *data, int64_t rows, int64_t cols, const double *aux, int64_t aux_rows,
                                     int64_t aux_cols) {
     if (!h || which < 0 || which > 1) return set_err(SMCMI_ERR_ARG, "bad argument");
     if (n_par > LIK_PAR_MAX) return set_err(SMCMI_ERR_ARG, "too many likelihood parameters");
     HIP_TRY(hipSetDevice(h->cfg.device));
+    drop_program(h, which);                                       // a device family (or none) replaces a registered program
     LikDev &l = h->h_model.lik[which];
     h->mem.release(&h->d_data[which]);
     h->mem.release(&h->d_aux[which]);
@@ -483,6 +494,7 @@ extern "C" int smcmi_set_likelihood_callback(smcmi_handle *h, int32_t which, smc
     HIP_TRY(hipSetDevice(h->cfg.device));
     h->cb[which] = fn; h->cb_ud[which] = user_data;
     h->dcb[which] = nullptr; h->dcb_ud[which] = nullptr;          // a host callback (or none) replaces a registered device callback
+    drop_program(h, which);                                       // ... or program
     LikDev &l = h->h_model.lik[which];
     h->mem.release(&h->d_data[which]);
     h->mem.release(&h->d_aux[which]);
@@ -498,6 +510,7 @@ extern "C" int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const
     smcmi_lik_device_fn fn = lik ? lik->fn : nullptr;
     h->dcb[which] = fn; h->dcb_ud[which] = fn ? lik->user_data : nullptr;
     h->cb[which] = nullptr; h->cb_ud[which] = nullptr;            // replaces a registered host callback or device family
+    drop_program(h, which);                                       // ... or program
     LikDev &l = h->h_model.lik[which];
     h->mem.release(&h->d_data[which]);
     h->mem.release(&h->d_aux[which]);
@@ -506,6 +519,65 @@ extern "C" int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const
     h->lik_host_data[which].clear(); h->lik_host_aux[which].clear();
     update_lik_prefix(h);
     if (which == 0) h->have_lik = fn != nullptr;
+    return push_model(h);
+}
+// ---- the same closure as HIP SOURCE, compiled at run time and called from a kernel of the engine's own (program.hip, progsrc.hpp)
+extern "C" int smcmi_program_compile(const char *source, const char *entry, const char *options, smcmi_program **out) {
+    std::string err;
+    const int rc = program::compile(source, entry, options, out, &err);
+    return rc ? set_err(rc, err) : 0;
+}
+extern "C" const char *smcmi_program_log(const smcmi_program *p) { return p ? p->log.c_str() : ""; }
+extern "C" int smcmi_program_code(const smcmi_program *p, const void **code, int64_t *size) {
+    if (!p || !p->ok) return set_err(SMCMI_ERR_ARG, "smcmi_program_code: no compiled program");
+    if (code) *code = p->code.data();
+    if (size) *size = (int64_t)p->code.size();
+    return 0;
+}
+extern "C" int smcmi_program_destroy(smcmi_program *p) {
+    delete p;
+    return 0;
+}
+extern "C" int smcmi_set_likelihood_program(smcmi_handle *h, int32_t which, const smcmi_program *p, const double *data, int64_t rows, int64_t cols,
+                                            const double *par, int64_t n_par) {
+    if (!h || which < 0 || which > 1) return set_err(SMCMI_ERR_ARG, "bad argument");
+    if (p && !p->ok) return set_err(SMCMI_ERR_ARG, "the program did not compile (smcmi_program_log): it cannot be registered");
+    if (p && (rows < 0 || cols < 0 || n_par < 0 || (!data && rows * cols > 0) || (!par && n_par > 0))) return set_err(SMCMI_ERR_ARG, "bad data / parameter shape");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    // everything the new registration needs is made first: a failure leaves the handle's previous likelihood as it was
+    program::Loaded mod;
+    double *d_data = nullptr, *d_par = nullptr;
+    if (p) {
+        std::string err;
+        if (int rc = program::load(p, &mod, &err)) return set_err(rc, err);
+        bool ok = h->d_prog_evals || dmalloc(h->mem, &h->d_prog_evals, (size_t)program::EVAL_WORDS) == 0;
+        if (ok && rows * cols > 0) ok = dmalloc(h->mem, &d_data, (size_t)(rows * cols)) == 0 && hipMemcpy(d_data, data, sizeof(double) * rows * cols, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok && n_par > 0) ok = dmalloc(h->mem, &d_par, (size_t)n_par) == 0 && hipMemcpy(d_par, par, sizeof(double) * n_par, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) ok = hipMemset(h->d_prog_evals, 0, sizeof(unsigned long long) * program::EVAL_WORDS) == hipSuccess && hipDeviceSynchronize() == hipSuccess;   // (null-stream copies)
+        if (!ok) {
+            program::unload(&mod);
+            h->mem.release(&d_data);
+            h->mem.release(&d_par);
+            (void)hipGetLastError();
+            return set_err(SMCMI_ERR_HIP, "device memory for the program's data / parameters");
+        }
+    }
+    drop_program(h, which);
+    h->cb[which] = nullptr; h->cb_ud[which] = nullptr;            // replaces a registered host callback, device callback or device family
+    h->dcb[which] = nullptr; h->dcb_ud[which] = nullptr;
+    if (p) {
+        h->prog[which] = mod;
+        h->d_prog_data[which] = d_data; h->d_prog_par[which] = d_par;
+        h->prog_rows[which] = rows; h->prog_cols[which] = cols; h->prog_npar[which] = n_par;
+    }
+    LikDev &l = h->h_model.lik[which];
+    h->mem.release(&h->d_data[which]);
+    h->mem.release(&h->d_aux[which]);
+    memset(&l, 0, sizeof(LikDev));
+    l.family = p ? SMCMI_LIK_HOST_CALLBACK : SMCMI_LIK_NONE;       // (to the kernels every kind of closure is "not evaluated here")
+    h->lik_host_data[which].clear(); h->lik_host_aux[which].clear();
+    update_lik_prefix(h);
+    if (which == 0) h->have_lik = p != nullptr;
     return push_model(h);
 }
 extern "C" int smcmi_eval_cloud_callback(smcmi_handle *h, int32_t which, int32_t column) {
@@ -1220,7 +1292,7 @@ extern "C" int smcmi_shard_mutate_partial(smcmi_handle *h, const double *mu_free
 #include "callback.hpp"
 extern "C" int smcmi_callback_phases(smcmi_handle *h, double *ms_out, int32_t n) {
     if (!h || !ms_out || n < 1) return set_err(SMCMI_ERR_ARG, "bad argument");
-    const double *ms = h->dcb[0] ? (h->dcbuf ? h->dcbuf->phase_ms : nullptr) : (h->cbuf ? h->cbuf->phase_ms : nullptr);
+    const double *ms = device_lik(h) ? (h->dcbuf ? h->dcbuf->phase_ms : nullptr) : (h->cbuf ? h->cbuf->phase_ms : nullptr);
     for (int k = 0; k < n; ++k) ms_out[k] = (ms && k < CBP_N) ? ms[k] : 0.0;
     return 0;
 }
@@ -1291,7 +1363,7 @@ extern "C" int smcmi_run_sharded(smcmi_handle *h, const smcmi_run_config *rc, sm
     res->segment_blocks = 0; res->segment_state = 0; res->segment_timeouts = 0; res->shift_fallback_stage = 0;
     if (!h->nccl && !h->has_hostc) return set_err(SMCMI_ERR_STATE, "smcmi_comm_init / smcmi_comm_init_host has not been called on this handle");
     if (int e = check_lik_pair(h)) return e;
-    if (h->dcb[0]) return set_err(SMCMI_ERR_UNSUPPORTED, "device likelihood callbacks serve one process (smcmi_run, smcmi_run_group); a multi-process run needs host callbacks or a device family");
+    if (device_lik(h)) return set_err(SMCMI_ERR_UNSUPPORTED, "device likelihood callbacks and compiled programs serve one process (smcmi_run, smcmi_run_group); a multi-process run needs host callbacks or a device family");
     ShardGroup g;
     g.hs = {h}; g.world = h->world; g.rccl = true; g.hostc = h->has_hostc;
     RunPlan p;
@@ -1387,6 +1459,7 @@ extern "C" int smcmi_destroy(smcmi_handle *h) {
     delete h->e2;
     delete h->cbuf;
     delete h->dcbuf;
+    for (int w = 0; w < 2; ++w) program::unload(&h->prog[w]);   // (the handle's own modules; their data is the owner's)
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;                                 // (its owner gives back every buffer the handle made)
     return 0;

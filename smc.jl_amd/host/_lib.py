@@ -21,7 +21,9 @@ PRIOR = {"normal": 0, "uniform": 1, "gamma": 2, "beta": 3, "invgamma": 4, "rooti
 LIK = {"none": -1, "gauss_iso": 0, "linreg": 1, "linmodel3": 2, "capm_literal": 3, "lgss_kalman": 4, "host_callback": 100}
 RESAMPLE = {"systematic": 0, "multinomial": 1, "polyalgo": 1}
 
-ERRORS = {-1: "ARG", -2: "HIP", -3: "NAN_ESS", -4: "POSDEF", -5: "CAPACITY", -6: "BRACKET", -7: "UNSUPPORTED", -8: "STATE", -9: "CALLBACK", -10: "TIMEOUT"}
+ERRORS = {-1: "ARG", -2: "HIP", -3: "NAN_ESS", -4: "POSDEF", -5: "CAPACITY", -6: "BRACKET", -7: "UNSUPPORTED", -8: "STATE", -9: "CALLBACK", -10: "TIMEOUT", -11: "COMPILE"}
+
+ERR_COMPILE = -11
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -98,6 +100,12 @@ SYMBOLS = [
     ("smcmi_set_likelihood", C.c_int, [_H, C.c_int32, C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int64]),
     ("smcmi_set_likelihood_callback", C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p]),
     ("smcmi_set_likelihood_device", C.c_int, [_H, C.c_int32, C.c_void_p]),      # const smcmi_device_likelihood * (C.byref(DeviceLik) or None)
+    # likelihoods compiled at run time from HIP source: smcmi_program * is an opaque pointer, the code object a (pointer, size) pair
+    ("smcmi_program_compile", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("smcmi_program_log", C.c_char_p, [C.c_void_p]),
+    ("smcmi_program_code", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), lp]),
+    ("smcmi_program_destroy", C.c_int, [C.c_void_p]),
+    ("smcmi_set_likelihood_program", C.c_int, [_H, C.c_int32, C.c_void_p, dp, C.c_int64, C.c_int64, dp, C.c_int64]),
     ("smcmi_eval_cloud_callback", C.c_int, [_H, C.c_int32, C.c_int32]),
     ("smcmi_callback_stats", C.c_int, [_H, lp, lp]),
     ("smcmi_callback_phases", C.c_int, [_H, dp, C.c_int32]),

@@ -203,14 +203,36 @@ class TorchLikelihood:
         return lambda th: fn(th, dat)
 
 
+class HIPLikelihood:
+    """A user likelihood given as HIP source, compiled by the library at run time (Engine.compile_program; no torch, no toolchain):
+    `source` defines `__device__ double loglik(const double *theta, long long ld, int d, const double *data, long long rows,
+    long long cols, const double *par, long long n_par)` with theta[j * ld] parameter j of the proposal.  smc(HIPLikelihood(source),
+    parameters, data, ...) hands `data` (2-d, column-major on the device) and `par` to the function and routes it through
+    Engine.set_likelihood_program: one launch per MH step x block, nothing read by the host."""
+
+    def __init__(self, source, par=None, entry="loglik", options=None):
+        if not isinstance(source, (str, bytes)):
+            raise TypeError("HIPLikelihood takes the likelihood's HIP source as text")
+        self.source, self.par, self.entry, self.options = source, par, entry, options
+        self._program = None
+
+    def program(self):
+        """the compiled program (compiled on first use; a compiler error raises CompileError with the log)"""
+        if self._program is None:
+            self._program = Engine.compile_program(self.source, entry=self.entry, options=self.options)
+        return self._program
+
+
 def _lik_kind(lik):
-    """'family' (device family), 'host' (Python callable) or 'device' (TorchLikelihood) of a likelihood spec tuple"""
-    return {"host_callback": "host", "device_callback": "device"}.get(lik[0], "family")
+    """'family' (device family), 'host' (Python callable) or 'device' (TorchLikelihood, HIPLikelihood) of a likelihood spec tuple"""
+    return {"host_callback": "host", "device_callback": "device", "program": "device"}.get(lik[0], "family")
 
 
 def _lik_spec(lik, data):
     if isinstance(lik, DeviceLikelihood):
         return lik.spec(data)
+    if isinstance(lik, HIPLikelihood):
+        return ("program", [], None, None)
     return ("device_callback" if isinstance(lik, TorchLikelihood) else "host_callback", [], None, None)
 
 
@@ -525,8 +547,8 @@ def smc_ensemble(loglikelihood, parameters, data, seeds, *, n_parts=5000, n_bloc
     from .engine import run_ensemble
 
     if not isinstance(loglikelihood, DeviceLikelihood):
-        raise NotImplementedError("smc_ensemble() takes a device likelihood (GaussIso, LinReg, LinModel3, CapmLiteral); a Python callable "
-                                  "or a TorchLikelihood runs through smc(), one seed per call")
+        raise NotImplementedError("smc_ensemble() takes a device likelihood (GaussIso, LinReg, LinModel3, CapmLiteral); a Python callable, "
+                                  "a TorchLikelihood or a HIPLikelihood runs through smc(), one seed per call")
     if verbose not in VERBOSITY:
         raise ValueError("verbose must be one of :none, :low, :high")
     if resampling_method not in ("systematic", "multinomial", "polyalgo"):
@@ -671,6 +693,8 @@ def _set_lik_on(e, lik, fn, data, which, device):
         e.set_likelihood_callback(_batch(fn, data), which=which)
     elif lik[0] == "device_callback":
         e.set_likelihood_device(fn.bind(data, device), which=which)
+    elif lik[0] == "program":
+        e.set_likelihood_program(fn.program(), data=data, par=fn.par, which=which)
     else:
         e.set_likelihood(*lik, which=which)
 

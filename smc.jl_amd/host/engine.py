@@ -24,6 +24,53 @@ def _i(a):
     return a.ctypes.data_as(ip)
 
 
+class CompileError(_lib.SMCMIError):
+    """a likelihood source did not compile; .log is the compiler's log (line numbers are those of the source, file likelihood.hip)"""
+
+    def __init__(self, code, msg, log):
+        super().__init__(code, msg + ("\n" + log if log else ""))
+        self.log = log
+
+
+class Program:
+    """A likelihood compiled from HIP source (include/smcmi.h smcmi_program_*): host memory only, tied to no engine and no device."""
+
+    def __init__(self, source, entry="loglik", options=None):
+        L = _lib.lib()
+        self._L, self._p = L, C.c_void_p()
+        enc = lambda s: None if s is None else s.encode() if isinstance(s, str) else bytes(s)
+        rc = L.smcmi_program_compile(enc(source), enc(entry), enc(options), C.byref(self._p))
+        if rc != 0:
+            msg = L.smcmi_last_error().decode()
+            log = L.smcmi_program_log(self._p).decode(errors="replace") if self._p else ""
+            self.close()
+            if rc == _lib.ERR_COMPILE:
+                raise CompileError(rc, msg, log)
+            raise _lib.SMCMIError(rc, msg)
+
+    @property
+    def log(self):
+        return self._L.smcmi_program_log(self._p).decode(errors="replace")
+
+    @property
+    def code(self):
+        """the gfx950 code object (bytes), for callers that cache"""
+        ptr, size = C.c_void_p(), C.c_int64()
+        check(self._L.smcmi_program_code(self._p, C.byref(ptr), C.byref(size)))
+        return C.string_at(ptr, size.value)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self._L.smcmi_program_destroy(self._p)
+        self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, n_parts, n_para, seed=0, device=0, max_stages=300, store_history=True, n_local=None, gid0=0):
         self._L = _lib.lib()
@@ -132,6 +179,33 @@ class Engine:
         st = _lib.DeviceLik(cb, None)
         self._cb[which] = (cb, st)
         check(self._L.smcmi_set_likelihood_device(self._h, which, C.byref(st)))
+
+    @staticmethod
+    def compile_program(source, entry="loglik", options=None):
+        """Compile a likelihood given as HIP source (smcmi_program_compile; needs no GPU and no engine): the source defines
+        `__device__ double loglik(const double *theta, long long ld, int d, const double *data, long long rows, long long cols,
+        const double *par, long long n_par)` with theta[j * ld] parameter j of the proposal.  Returns a Program; a compiler error
+        raises CompileError, whose .log has the compiler's messages with the line numbers of `source` (likelihood.hip:<line>)."""
+        return Program(source, entry=entry, options=options)
+
+    def set_likelihood_program(self, program_or_source, data=None, par=None, which=0):
+        """Register a compiled likelihood (smcmi_set_likelihood_program): a Program, or source text that is compiled first.  data (2-d,
+        passed column-major) and par become the function's `data` / `par` on the device.  None unregisters.  The handle keeps its own
+        module: the Program may be closed right away."""
+        if program_or_source is None:
+            check(self._L.smcmi_set_likelihood_program(self._h, which, None, None, 0, 0, None, 0))
+            return
+        own = not isinstance(program_or_source, Program)
+        prog = Program(program_or_source) if own else program_or_source
+        try:
+            par = _f64(() if par is None else par).ravel()
+            data = None if data is None else np.asfortranarray(np.atleast_2d(np.asarray(data, dtype=np.float64)))
+            check(self._L.smcmi_set_likelihood_program(
+                self._h, which, prog._p, None if data is None or data.size == 0 else _d(data), 0 if data is None else data.shape[0],
+                0 if data is None else data.shape[1], _d(par) if par.size else None, par.size))
+        finally:
+            if own:
+                prog.close()
 
     def eval_cloud_callback(self, which=0, column=None):
         self._checked(self._L.smcmi_eval_cloud_callback(self._h, which, self.d if column is None else int(column)))

@@ -24,7 +24,7 @@ import JLD2, HDF5, LinearAlgebra
 export smc, Cloud, get_vals, get_loglh, get_logprior, get_old_loglh, get_logpost, get_accept, get_weights, weighted_mean, weighted_cov,
        weighted_std, weighted_quantile, weighted_quantiles, get_likeliest_particle_value, get_highest_posterior_particle_value,
        device_weighted_quantiles, device_weighted_quantiles_group, device_best_particle, device_best_particle_group,
-       cloud_isempty, GaussIso, LinReg, LinModel3, CapmLiteral, LGSSKalman,
+       cloud_isempty, GaussIso, LinReg, LinModel3, CapmLiteral, LGSSKalman, HIPLikelihood,
        mutation, resample, mvnormal_mixture_draw, initial_draw!, get_cloud                       # src/SMC.jl:13-17
 
 const LIB = get(ENV, "SMCMI_LIB", joinpath(@__DIR__, "..", "csrc", "libsmcmi.so"))
@@ -149,6 +149,47 @@ lik_aux(l::LinModel3) = l.X; lik_aux(l::CapmLiteral) = l.market
 lik_aux(l::LGSSKalman) = reshape(vcat(vec(l.C'), vec(l.R'), vec(l.Z')), 1, :)          # [C 8x8 | R 8x3 | Z 3x8] row-major, 112 doubles
 lik_aux(::Any) = zeros(0, 0)
 
+# ---- the closure as HIP SOURCE, compiled by the library at run time (smcmi_program_* in smcmi.h): a likelihood on the GPU without
+# CUDA.jl / AMDGPU.jl or a toolchain.  `source` defines
+#   __device__ double loglik(const double *theta, long long ld, int d, const double *data, long long rows, long long cols,
+#                            const double *par, long long n_par)
+# with theta[j * ld] parameter j (0-based) of the proposal; `data` is the matrix given to smc (column-major), `par` the vector below.
+# smc(HIPLikelihood(source; par = [...]), parameters, data; kwargs...) runs it; old_loglikelihood may be another HIPLikelihood.
+struct HIPLikelihood
+    source::String
+    par::Vector{Float64}
+    entry::String
+    options::Union{Nothing, String}
+end
+HIPLikelihood(source::AbstractString; par = Float64[], entry = "loglik", options = nothing) =
+    HIPLikelihood(String(source), Float64[x for x in par], String(entry), options)
+const Program = Ptr{Cvoid}                                   # smcmi_program *
+struct CompileError <: Exception
+    code::Int
+    log::String
+end
+Base.showerror(io::IO, e::CompileError) = print(io, "SMCMI: the likelihood source did not compile (", e.code, ")\n", e.log)
+function compile_program(lik::HIPLikelihood)
+    p = Ref{Program}(C_NULL)
+    opts = lik.options === nothing ? Cstring(C_NULL) : lik.options
+    rc = ccall((:smcmi_program_compile, LIB), Cint, (Cstring, Cstring, Cstring, Ref{Program}), lik.source, lik.entry, opts, p)
+    if rc != 0
+        log = p[] == C_NULL ? "" : unsafe_string(ccall((:smcmi_program_log, LIB), Cstring, (Ptr{Cvoid},), p[]))
+        p[] == C_NULL || ccall((:smcmi_program_destroy, LIB), Cint, (Ptr{Cvoid},), p[])
+        rc == -11 ? throw(CompileError(rc, log)) : check(rc)
+    end
+    p[]
+end
+function set_program!(h::Handle, lik::HIPLikelihood, data::Matrix{Float64}, which::Integer)
+    p = compile_program(lik)
+    try
+        check(ccall((:smcmi_set_likelihood_program, LIB), Cint, (Handle, Int32, Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64),
+                    h, which, p, data, size(data, 1), size(data, 2), lik.par, length(lik.par)))
+    finally
+        ccall((:smcmi_program_destroy, LIB), Cint, (Ptr{Cvoid},), p)          # (the handle keeps its own module)
+    end
+end
+
 prior_code(d::Normal) = (Int32(0), d.μ, d.σ)
 prior_code(d::Uniform) = (Int32(1), d.a, d.b)
 prior_code(d::Gamma) = (Int32(2), shape(d), scale(d))
@@ -200,6 +241,8 @@ function set_model!(h::Handle, parameters, lik, data, which::Integer, keep::Vect
         check(ccall((:smcmi_set_likelihood, LIB), Cint,
                     (Handle, Int32, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64),
                     h, which, family(lik), par, length(par), data, size(data, 1), size(data, 2), aux, size(aux, 1), size(aux, 2)))
+    elseif lik isa HIPLikelihood
+        set_program!(h, lik, data, which)                   # smc(::HIPLikelihood, parameters, data; ...): compiled, registered, run on the GPU
     else
         env = CallbackEnv(lik, parameters, data, toggle)
         push!(keep, env)                                    # rooted for the lifetime of the handle
@@ -258,7 +301,8 @@ stage_path(savepath, i) = replace(savepath, ".jld2" => "_stage=$(i).jld2")      
 Drop-in for `SMC.smc` (src/smc_main.jl:118-161): same positional arguments, same keyword list, same files - `savepath` receives
 `cloud`, `w`, `W` (JLD2) and `particle_store_path` the `smcparams` matrix (HDF5), intermediate saves go to
 `savepath` with `_stage=i` (smc_main.jl:499-507, 513-526).  `loglikelihood` is the user's closure
-`loglikelihood(parameters::ParameterVector, data::Matrix{Float64})::Float64` or one of the `DeviceLikelihood` structs.
+`loglikelihood(parameters::ParameterVector, data::Matrix{Float64})::Float64`, one of the `DeviceLikelihood` structs, or a
+`HIPLikelihood` (the likelihood as HIP source, compiled at run time and evaluated on the GPU: `smc(::HIPLikelihood, parameters, data; ...)`).
 Returns `(cloud, w, W)` in addition to writing the files (the reference returns nothing, quirk Q8).
 `regime_switching = true` samples the extra regime values as additional columns (a device family then takes the flattened vector); `parallel` is moot (the device is
 the parallelism).
