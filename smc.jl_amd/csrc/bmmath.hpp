@@ -124,3 +124,47 @@ BM_FN void bm_normal_pair(double ua, double ub, double *z0, double *z1) {
     *z0 = r * c;
     *z1 = r * s;
 }
+
+// ---- y / b for a divisor that is the same in every lane, from its reciprocal formed once on the host.
+//
+// bm_div_rb(y, b, rb, b_ok) returns the bits of `y / b` (IEEE round to nearest), given rb = 1.0 / b as an IEEE division rounds it
+// (rb = RN(1 / b)) and b_ok = bm_div_rb_admits(b).  The hardware's division spends a reciprocal estimate, four FMAs refining 1 / b and two
+// scalings on the DIVISOR before the dividend takes part; here that work is done once per model and a quotient costs a product and two
+// residual / correction pairs:
+//     q0 = RN(y rb)                                   |q0 - y/b| <= 2 ulp or so: rb carries half an ulp, the product another half
+//     r0 = RN(y - q0 b)   q1 = RN(q0 + r0 rb)         q1 = RN(t) for a t within 2^-100 (relative) of y/b: a FAITHFUL rounding of y/b - one
+//                                                     of the two doubles that bracket it (r0 itself may round: q0 b can be 55 bits from y's
+//                                                     last place, which costs 2^-53 of a 2^-52 correction)
+//     r1 = y - q1 b       q  = RN(q1 + r1 rb)         r1 is EXACT for a faithful q1 (a multiple of ulp(q1) ulp(b) below |b| ulp(q1): 53
+//                                                     bits), and by Markstein's theorem (P. Markstein, "Computation of elementary functions
+//                                                     on the IBM RISC System/6000 processor", IBM J. Res. Dev. 34 (1990); Muller et al.,
+//                                                     Handbook of Floating-Point Arithmetic, 2nd ed., Theorem 4.9) q = RN(y / b) whenever
+//                                                     rb = RN(1 / b), q1 is faithful, r1 is exact and nothing under- or overflows.
+// Admitted (everything else takes `/` itself, so the bits are those of `/` for every input):
+//     2^-500 <= |b| <= 2^500    rb is a normal number in the same range
+//     2^-460 <= |y| <= 2^500    the quotient lies in [2^-960, 2^1000]: normal, and the residuals' last place (2^-105 |y| >= 2^-565) is far
+//                               above the subnormals, so both FMAs that form them are exact where the argument needs it
+// y = +-0 is NOT admitted: the residual of a zero quotient is +0 whatever the quotient's sign, and (-0) + (+0) = +0 would lose the sign
+// of -0 / b.  Infinities and NaN fail the range test as well (every comparison with NaN is false).
+// Explicit fma only: the strict library and the product build give the same bits.  Checked bit for bit against `/` by
+// tests/test_divrb_cpu.py (tests/divrb_check.c includes THIS file).
+#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
+#define BM_HD __host__ __device__ inline
+#define BM_FABS(x) __builtin_fabs(x)
+#else
+#define BM_HD static inline
+#define BM_FABS(x) fabs(x)
+#endif
+#define BM_DIV_B_MIN 0x1p-500
+#define BM_DIV_B_MAX 0x1p+500
+#define BM_DIV_Y_MIN 0x1p-460
+#define BM_DIV_Y_MAX 0x1p+500
+BM_HD int bm_div_rb_admits(double b) { const double ab = BM_FABS(b); return ab >= BM_DIV_B_MIN && ab <= BM_DIV_B_MAX; }
+BM_HD int bm_div_rb_admits_y(double y) { const double ay = BM_FABS(y); return ay >= BM_DIV_Y_MIN && ay <= BM_DIV_Y_MAX; }
+// the quotient of an admitted pair
+BM_HD double bm_div_rb_core(double y, double b, double rb) {
+    double q = y * rb;
+    q = BM_FMA(BM_FMA(-q, b, y), rb, q);
+    return BM_FMA(BM_FMA(-q, b, y), rb, q);
+}
+BM_HD double bm_div_rb(double y, double b, double rb, int b_ok) { return (b_ok && bm_div_rb_admits_y(y)) ? bm_div_rb_core(y, b, rb) : y / b; }

@@ -43,7 +43,15 @@ struct ModelDev {
     double prior_a[MAXD], prior_b[MAXD];
     double prior_k[MAXD];      // family constant precomputed on the host (e.g. log σ, -log(b-a))
     LikDev lik[2];             // [0] loglikelihood/data, [1] old_loglikelihood/old_data
+    // appended behind everything else (no other member's offset moves): what the segment kernel's MH step reads of the priors beyond the
+    // above (kernels.hpp eval_target<D, true>)
+    double prior_rb[MAXD];     // 1.0 / prior_b[k] as the host's division rounds it, where bmmath.hpp bm_div_rb admits prior_b[k]; else 0
+    int prior_shape;           // PRIOR_* bits below
+    int pad_;
 };
+// what the host knows about a model's priors as a whole (ModelDev::prior_shape; Mut2Args::has_other of the segment launches that read it)
+constexpr int PRIOR_HAS_OTHER = 1;    // = has_other_priors
+constexpr int PRIOR_NORMAL_RB = 2;    // no parameter is fixed, every prior is Normal and every sd has its reciprocal in prior_rb
 
 enum SolveMode { MODE_IDLE = 0, MODE_SCAN = 1, MODE_SECTION = 2, MODE_FINAL = 3 };
 

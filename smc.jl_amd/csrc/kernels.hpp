@@ -2753,14 +2753,24 @@ __device__ inline void expand_alpha1_factor(double *Ls, const double *L, const i
 }
 // The target at the proposal x: log-prior, log-likelihood on the new data (-Inf there takes the prior with it) and on the old data; the
 // three stay -Inf outside the bounds.  debug & 2: a stub that needs no model (parity tests of the draws).
-template <int D>
+// TGT (the segment kernel's α = 1 units; stage2.hpp A1F_BOUNDS = TGT_BOUNDS << 4, A1F_PRIOR = TGT_PRIOR << 4): the same values bit for bit from
+// fewer instructions (model.hpp) - TGT_BOUNDS: the bounds without their chain of branches; TGT_PRIOR: has_other carries the model's PRIOR_*
+// bits and mv.rb is set: the Normal-only log-prior where the model allows it.
+constexpr int TGT_BOUNDS = 1, TGT_PRIOR = 2;
+template <int D, int TGT = 0>
 __device__ __forceinline__ void eval_target(const ModelView &mv, const LikView (&lv)[2], int has_other, int debug, const double (&x)[D], double zz2,
                                             double like, double lprior, double &prior_new, double &like_new, double &like_old_data) {
 SMCMI_FP_CONTRACT
     auto XN = [&](int k) { return x[k]; };
+    auto inside = [&]() { if constexpr ((TGT & TGT_BOUNDS) != 0) return in_bounds_flat<D>(mv, XN); else return in_bounds_s<D>(mv, XN); };
+    auto prior = [&]() {
+        if constexpr ((TGT & TGT_PRIOR) != 0)
+            return (has_other & PRIOR_NORMAL_RB) ? logprior_normal_rb<D>(mv, XN) : logprior_s<D>(mv, XN, has_other & PRIOR_HAS_OTHER);
+        else return logprior_s<D>(mv, XN, has_other);
+    };
     if (debug & 2) { prior_new = lprior - 0.1 * zz2; like_new = like - 0.2; like_old_data = 0.0; }
-    else if (in_bounds_s<D>(mv, XN)) {
-        prior_new = logprior_s<D>(mv, XN, has_other);
+    else if (inside()) {
+        prior_new = prior();
         like_new = loglik_s<D>(lv[0], XN);
         if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
         like_old_data = (lv[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik_s<D>(lv[1], XN);
@@ -2769,8 +2779,8 @@ SMCMI_FP_CONTRACT
 // One proposal of one particle (src/mutation.jl:86-138; helpers.jl:87-164 for α < 1): from the block's normals z, the mixture uniform uc
 // and the MH uniform step_prob to the updated (x, like, lprior, like_prev, accept).  Ls: the block's factor as expand_alpha1_factor leaves
 // it and logdet_b its log-determinant (α = 1); M: the block's dense mixture matrices (α < 1; MixDense in LDS or MixDenseC through the
-// constant address space); zt: this thread's private LDS column, stride T (α < 1).
-template <int D, bool ALPHA1, int T, class MX, class PH = NoPhase>
+// constant address space); zt: this thread's private LDS column, stride T (α < 1).  TGT: eval_target's.
+template <int D, bool ALPHA1, int T, int TGT = 0, class MX, class PH = NoPhase>
 __device__ __forceinline__ void mh_step(const double *Ls, double logdet_b, int db, const MX &M, const LikView (&lv)[2], const ModelView &mv, int has_other,
                                         int debug, double c_alpha, double phi_n, double *zt, const double (&z)[D], double uc, double step_prob,
                                         double (&x)[D], double &like, double &lprior, double &like_prev, double &accept, const PH &ph = PH{}) {
@@ -2814,7 +2824,7 @@ SMCMI_FP_CONTRACT
 #pragma unroll
         for (int k = 0; k < D; ++k) { xo[k] = x[k]; x[k] = xn[k]; }
     }
-    eval_target<D>(mv, lv, has_other, debug, x, zz2, like, lprior, prior_new, like_new, like_old_data);
+    eval_target<D, TGT>(mv, lv, has_other, debug, x, zz2, like, lprior, prior_new, like_new, like_old_data);
     ph.template at<7>();
     const double eta = exp(phi_n * (like_new - like) + (1.0 - phi_n) * (like_old_data - like_prev) +
                            (prior_new - lprior) + (q0 - q1));

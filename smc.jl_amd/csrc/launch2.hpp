@@ -122,7 +122,9 @@ int launch_k3_seg(smcmi_handle *h, const Mut2Args &ma, const Seg3Args &sa, int n
         if (set_max_lds(k3_segment<D, A1, RIDE, 1, SYS>, k3_max_lds_bytes(D, A1, 1))) return SMCMI_ERR_HIP;
         e->seg_attr_set |= attr_bit;
     }
-    k3_segment<D, A1, RIDE, 1, SYS><<<grid, T3, lds, h->stream>>>(h->cl, h->d_st, e->d_ctl, h->d_model, e->g, ma, sa, nb, h->h_model.n_free);
+    Mut2Args mk = ma;
+    if constexpr ((k3_fast_bits(A1, RIDE, 1, SYS) & A1F_PRIOR) != 0) mk.has_other = h->h_model.prior_shape;      // (this unit's MH step reads the PRIOR_* bits)
+    k3_segment<D, A1, RIDE, 1, SYS><<<grid, T3, lds, h->stream>>>(h->cl, h->d_st, e->d_ctl, h->d_model, e->g, mk, sa, nb, h->h_model.n_free);
     }
     return 0;
 }

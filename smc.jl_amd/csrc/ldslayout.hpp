@@ -61,7 +61,8 @@ constexpr size_t D8 = sizeof(double), I4 = sizeof(int);
 // then the scratch of engine 2's prologue (k2_prologue: totals, covariance, factorisation)
 enum Mut2Id {
     M_Ls,                                 // [D*D] row-major with stride D, identity-padded
-    M_mu, M_sdd, M_sdn,                   // [D] each: kept in place, no kernel reads them
+    M_mu, M_sdd, M_rb = M_sdd, M_sdn,     // [D] each: kept in place, no kernel reads them - but the segment kernel's MH step, which keeps
+                                          // the Normal priors' reciprocal sds in the second (M_rb: ModelDev::prior_rb)
     M_red,                                // [red_n] the block reduction's wave sums (4 waves: k_mutate_reg; up to 8: engine 2)
     M_lo, M_hi, M_a, M_b, M_k,            // [D] each: bounds and prior constants
     M_lpar,                               // [2 * LIK_PAR_MAX]

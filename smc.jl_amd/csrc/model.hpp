@@ -10,6 +10,7 @@
 #include <math.h>
 #include <type_traits>
 
+#include "bmmath.hpp"
 #include "devstate.hpp"
 #include "ldslayout.hpp"
 
@@ -64,6 +65,7 @@ struct ModelView {
     int d;
     const int *fixed, *prior_family;
     const double *lo, *hi, *prior_a, *prior_b, *prior_k;
+    const double *rb = nullptr;      // ModelDev::prior_rb, set by the kernels whose MH step reads it (eval_target<D, true>)
 };
 struct LikView {
     int family;
@@ -132,6 +134,62 @@ __device__ inline double logprior_s(const M &m, Th th, int has_other) {
                 for (int q = 0; q < D; ++q) x = (q == k) ? th(q) : x;
                 s += prior_logpdf(fam, m.prior_a[k], m.prior_b[k], m.prior_k[k], x);
             }
+        }
+    }
+    return s;
+}
+
+// ---- the two above as the segment kernel's MH step runs them (kernels.hpp eval_target<D, true>): the same values, bit for bit, from
+// fewer instructions.
+// The bounds: `ok = ok && ...` above is compiled as 2 D nested branches - one LDS read of one bound, a full wait, one comparison, one branch
+// per step, and a particle inside its bounds (nearly every one) walks them all.  Here every bound is loaded before the first comparison
+// and the 2 D results are combined without a short circuit: one value, one branch at the caller.  The boolean is the same for every
+// input: the conjunction of the same 2 D comparisons (a NaN fails `lo <= x` and `x <= hi` either way).
+template <int D, class M, class Th>
+__device__ inline bool in_bounds_flat(const M &m, Th th) {
+    double lo[D], hi[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) { lo[k] = m.lo[k]; hi[k] = m.hi[k]; }
+    int ok = 1;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const double x = th(k);
+        ok &= (int)(lo[k] <= x) & (int)(x <= hi[k]);
+    }
+    return ok != 0;
+}
+// The log-prior of a model in which NO parameter is fixed, EVERY prior is Normal and every sd is one bm_div_rb admits (PRIOR_NORMAL_RB:
+// the host knows, smcmi_set_parameters).  logprior_s evaluates both densities of every parameter and picks with six selects; its
+// (x - a) / b is a full FP64 division - twelve instructions, seven of which and the slow reciprocal depend on b alone.  Here:
+//  - z = (x - a) / b by bm_div_rb_core(y, b, rb) with rb = m.rb[k] = RN(1 / b) from the host: the bits of the division (bmmath.hpp) while
+//    every y = x - a of the particle lies in the admitted range; a particle with one that does not (y = 0 exactly, |y| < 2^-460, an
+//    overflowed difference, NaN) takes `/` for all its parameters - a branch no wavefront of a real run takes;
+//  - the Normal term alone: in logprior_s a Normal, free parameter adds v = ln to s and every other one adds 0.0.  With no fixed and no
+//    other-family parameter every step is `s += ln_k` in ascending k from s = 0.0, which is what this loop does - no term is skipped, so
+//    the sign-of-zero question (s + 0.0 for s = -0.0) does not arise: s starts at +0.0 and a sum that is not exactly cancelled keeps
+//    its sign, an exactly cancelled one is +0.0 in round-to-nearest, both here and there.
+// The expression of ln is logprior_s's, token for token (no contraction in this header: the pragma is the callers').
+template <int D, class M, class Th>
+__device__ inline double logprior_normal_rb(const M &m, Th th) {
+    double y[D], b[D], rb[D];
+    int inr = 1;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        y[k] = th(k) - m.prior_a[k]; b[k] = m.prior_b[k]; rb[k] = m.rb[k];
+        inr &= bm_div_rb_admits_y(y[k]);
+    }
+    double s = 0.0;
+    if (__builtin_expect(inr != 0, 1)) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const double z = bm_div_rb_core(y[k], b[k], rb[k]);
+            s += -(z * z + LOG2PI) / 2.0 - m.prior_k[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const double z = y[k] / b[k];
+            s += -(z * z + LOG2PI) / 2.0 - m.prior_k[k];
         }
     }
     return s;

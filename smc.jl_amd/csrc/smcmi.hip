@@ -298,6 +298,16 @@ extern "C" int smcmi_set_parameters(smcmi_handle *h, const int32_t *fixed, const
             if (prior_family[k] > SMCMI_PRIOR_UNIFORM) m.has_other_priors = 1;
         }
     }
+    // the priors as a whole, for the kernels that read it (devstate.hpp PRIOR_*): 1 / sd of every Normal prior whose sd bm_div_rb admits - an
+    // IEEE division, so RN(1 / sd), which is what its proof needs
+    bool normal_rb = true;
+    for (int k = 0; k < MAXD; ++k) m.prior_rb[k] = 0.0;
+    for (int k = 0; k < h->d; ++k) {
+        const bool rb_ok = !m.fixed[k] && prior_family[k] == SMCMI_PRIOR_NORMAL && bm_div_rb_admits(prior_b[k]);
+        if (rb_ok) m.prior_rb[k] = 1.0 / prior_b[k];
+        normal_rb = normal_rb && rb_ok;
+    }
+    m.prior_shape = (m.has_other_priors ? PRIOR_HAS_OTHER : 0) | (normal_rb ? PRIOR_NORMAL_RB : 0);
     if (m.n_free == 0) return set_err(SMCMI_ERR_ARG, "All model parameters are fixed!");   // smc_main.jl:237
     h->have_params = true;
     return push_model(h);

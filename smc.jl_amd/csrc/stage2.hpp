@@ -1640,6 +1640,14 @@ constexpr int A1F_LS = 8;      // one random block: the Cholesky wavefront store
 #ifndef SMCMI_A1FAST
 #define SMCMI_A1FAST (A1F_SHUF | A1F_NOMIX | A1F_LOGDET | A1F_LS)
 #endif
+// ... and of the MH step's target (kernels.hpp eval_target's TGT_* << 4), which only the two-hand-over, one-handle, one-chunk units take
+// (stage3.hpp: the riding, two-chunk and several-handle units keep the code they had):
+constexpr int A1F_BOUNDS = 16; // the bounds check without its chain of 2 D branches (model.hpp in_bounds_flat)
+constexpr int A1F_PRIOR = 32;  // Mut2Args::has_other carries the PRIOR_* bits and the LDS view the reciprocal sds (lds::M_rb): the Normal-only log-prior
+#ifndef SMCMI_A1TARGET
+#define SMCMI_A1TARGET (A1F_BOUNDS | A1F_PRIOR)
+#endif
+static_assert(A1F_BOUNDS == (TGT_BOUNDS << 4) && A1F_PRIOR == (TGT_PRIOR << 4), "k2_mh_steps hands FAST >> 4 to mh_step");
 
 // jx_pre: shuffle_partner() of lane (threadIdx.x & 63), valid in wavefront 1 (threads 64..127)
 // CHM: rows of the in-register Cholesky (12 serves n_para <= 12; 16 the wide kernels)
@@ -1853,7 +1861,8 @@ __device__ inline void k2_bookkeeping(DevState *st, Ctl2 *ctl, const Mut2Args &m
 // dimension of ma.zbuf.  All threads call.
 // FAST (α = 1 only): A1F_LS - with one block L.Ls holds the expanded factor already (proposal2<.., FAST>); A1F_LOGDET - L.logdet_s is not
 // written: each wavefront forms the block's log-determinant from the diagonal of L.Lraw, the operations of proposal2 in their order (log of
-// each diagonal entry, added in ascending index from 0.0, times 2)
+// each diagonal entry, added in ascending index from 0.0, times 2); A1F_BOUNDS, A1F_PRIOR - mh_step's TGT (the caller has set mv.rb and
+// ma.has_other for A1F_PRIOR)
 template <int D, bool ALPHA1, int T, bool PREDRAW, bool ZPART = false, int FAST = 0>
 __device__ inline void k2_mh_steps(const Mut2Lds<D> &L, double *mixbuf, int *mixpos, double *mixzt, const Mut2Args &ma, long long ldz,
                                    const LikView (&lv)[2], const ModelView &mv, int nb, int nf, bool live, long long i, unsigned long long pid,
@@ -1900,8 +1909,8 @@ SMCMI_FP_CONTRACT
                     for (int e = 0; e < D; ++e) z[e] = zt[(long long)(2 + e) * ldz];
                 }
             } else if (!PREDRAW || t != 0) mh_draw<D>(ma.seed, pid, stage, t, db, step_prob, uc, z);   // (proposal 0 may have been drawn ahead of the prologue)
-            mh_step<D, ALPHA1, T>(Ls, (FAST & A1F_LOGDET) != 0 ? logdet_w : logdet_s[b], db, MX, lv, mv, has_other, ma.debug, c_alpha, phi_n, mixzt + tid, z, uc,
-                                  step_prob, x, like, lprior, like_prev, accept);
+            mh_step<D, ALPHA1, T, ((FAST >> 4) & 3)>(Ls, (FAST & A1F_LOGDET) != 0 ? logdet_w : logdet_s[b], db, MX, lv, mv, has_other, ma.debug, c_alpha, phi_n,
+                                                     mixzt + tid, z, uc, step_prob, x, like, lprior, like_prev, accept);
         }
     }
 }

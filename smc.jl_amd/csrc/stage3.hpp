@@ -1271,6 +1271,11 @@ __device__ inline bool k3_rides(const RunParams &rp, const Seg3Args &sa, const P
 // 512-particle chunks of its virtual shard - one in registers, one parked in LDS ((D + 6) columns behind the parking area), exchanged between
 // the per-particle phases; it publishes two rows per hand-over and pays the serial phases and the hand-overs once.  A stage that must resample
 // does so in place (k3_select_two).
+// the A1F_* bits of an instantiation: the α = 1 fast path, and the MH step's target (A1F_BOUNDS, A1F_PRIOR) in the two-hand-over, one-handle,
+// one-chunk unit alone - the launcher (launch2.hpp launch_k3_seg) hands that one the model's PRIOR_* bits in Mut2Args::has_other
+constexpr int k3_fast_bits(bool alpha1, bool ride, int ch, bool sys) {
+    return alpha1 ? ((SMCMI_A1FAST) | ((!ride && ch == 1 && !sys) ? (SMCMI_A1TARGET) : 0)) : 0;
+}
 template <int D, bool ALPHA1, bool RIDE, int CH = 1, bool SYS = false>
 __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, DevState *st, Ctl2 *ctl, const ModelDev *md, Geo2 g, Mut2Args ma, Seg3Args sa, int nb, int nf) {
     constexpr int NPF = Mut2Lds<D>::NPF, MCM = pad2(NPF);
@@ -1293,7 +1298,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     Mut2Lds<D> L(sm);
     constexpr lds::Seg3Layout O3 = k3_layout(D, ALPHA1, CH);
     const int tid = threadIdx.x;
-    constexpr int FAST = ALPHA1 ? (SMCMI_A1FAST) : 0;           // proposal2's α = 1 fast path (stage2.hpp A1F_*)
+    constexpr int FAST = k3_fast_bits(ALPHA1, RIDE, CH, SYS);   // proposal2's and k2_mh_steps' α = 1 fast path (stage2.hpp A1F_*)
 #ifdef SMCMI_K3_CH2
     const int W = g.Vl * ((g.nb2 + CH - 1) / CH);               // (workers per virtual shard: every one owns CH blocks of it)
 #else
@@ -1572,6 +1577,11 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     }
     for (int k = tid; k < 2 * LIK_PAR_MAX; k += T3) L.l_par[k] = md->lik[k / LIK_PAR_MAX].par[k % LIK_PAR_MAX];
     ModelView mv{D, L.m_fix, L.m_fam, L.m_lo, L.m_hi, L.m_a, L.m_b, L.m_k};
+    if constexpr ((FAST & A1F_PRIOR) != 0) {                    // the Normal priors' reciprocal sds, in D doubles of the layout no kernel reads
+        double *m_rb = lds_at<double, lds::mut2(D)[lds::M_rb]>(sm);
+        for (int k = tid; k < D; k += T3) m_rb[k] = md->prior_rb[k];
+        mv.rb = m_rb;
+    }
     LikView lv[2];
     stage_lik(ma.lik[0], ma.lik[1], L.l_par, L.l_dat, T3, lv);     // once per segment (the mutation rows' scratch is `red`, not this area)
     const int db0 = nb == 1 ? nf : (nf + nb - 1) / nb;          // entries of the first random block

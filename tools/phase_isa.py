@@ -17,7 +17,15 @@ and counts the instructions between two consecutive ones by mnemonic prefix:
 The text is cut in layout order, which for this kernel is program order; a rarely taken branch laid out between two stamps counts in that
 phase.  Counts are static: a loop body counts once.  A counting aid - it checks nothing.
 
-usage: python tools/phase_isa.py <device.s> <mangled kernel name prefix> [--json]"""
+--blocks FROM TO prints the census of ONE phase (the text between the stamps of slots FROM and TO) per basic block - the text between two
+labels - with the columns above and two more:
+
+  lds_read ds_read*
+  div      v_div_fixup* (one per division the compiler expanded)
+
+so that a block such as the MH step's bounds check + log-prior can be read off without a script of one's own.
+
+usage: python tools/phase_isa.py <device.s> <mangled kernel name prefix> [--json] [--blocks FROM TO]"""
 import json
 import re
 import sys
@@ -122,6 +130,44 @@ def phase_table(asm, prefix):
     return {"spill_vgprs": sorted(spills, key=lambda r: int(r[1:]) if r[1:].isdigit() else -1), "phases": phases, "loop": loop}
 
 
+BLOCK_COLUMNS = COLUMNS + ("lds_read", "div")
+
+
+def block_table(asm, prefix, slot_from, slot_to):
+    """[{"label": ..., <column>: count ...}] for the basic blocks (label to label, layout order) of the first phase that runs from a stamp of
+    slot_from to the next stamp, which must be of slot_to; the text in front of the phase's first label counts under "(entry)"."""
+    lines = kernel_text(asm, prefix)
+    spills = spill_vgprs(lines)
+    st = stamps(lines)
+    span = next(((a, b) for (a, sa), (b, sb) in zip(st, st[1:]) if sa == slot_from and sb == slot_to), None)
+    if span is None:
+        raise ValueError("no phase %s->%s" % (slot_from, slot_to))
+    rows = [dict({"label": "(entry)"}, **{c: 0 for c in BLOCK_COLUMNS})]
+    for ln in lines[span[0] + 1:span[1]]:
+        t = ln.split(";")[0].strip()
+        if t.endswith(":") and " " not in t:
+            rows.append(dict({"label": t[:-1]}, **{c: 0 for c in BLOCK_COLUMNS}))
+            continue
+        ins = _instruction(ln)
+        if not ins:
+            continue
+        for c in classify(ins[0], ins[1], spills):
+            rows[-1][c] += 1
+        if ins[0].startswith("ds_read"):
+            rows[-1]["lds_read"] += 1
+        if ins[0].startswith("v_div_fixup"):
+            rows[-1]["div"] += 1
+    return rows
+
+
+def render_blocks(rows):
+    out = ["%-14s" % "block" + "".join("%9s" % c for c in BLOCK_COLUMNS)]
+    for r in rows:
+        out.append("%-14s" % r["label"] + "".join("%9d" % r[c] for c in BLOCK_COLUMNS))
+    out.append("%-14s" % "phase" + "".join("%9d" % sum(r[c] for r in rows) for c in BLOCK_COLUMNS))
+    return "\n".join(out)
+
+
 def render(table):
     head = "%-10s" % "stamps" + "".join("%8s" % c for c in COLUMNS)
     rows = [head]
@@ -135,5 +181,10 @@ def render(table):
 if __name__ == "__main__":
     if len(sys.argv) < 3:
         sys.exit(__doc__)
+    if "--blocks" in sys.argv[3:]:
+        at = sys.argv.index("--blocks")
+        rows = block_table(open(sys.argv[1]).read(), sys.argv[2], int(sys.argv[at + 1]), int(sys.argv[at + 2]))
+        print(json.dumps(rows, indent=1) if "--json" in sys.argv[3:] else render_blocks(rows))
+        sys.exit(0)
     tab = phase_table(open(sys.argv[1]).read(), sys.argv[2])
     print(json.dumps(tab, indent=1) if "--json" in sys.argv[3:] else render(tab))
