@@ -22,8 +22,17 @@ static int prof2_report(smcmi_handle *h0, const Geo2 &g0, int seg_launches) {
                 if (sp[9]) fprintf(stderr, "[smcmi3]   selection inside the segment (wall clock, us): particle stored %.2f | chunk offsets %.2f | scan + cum %.2f | stores acknowledged %.2f | hand-over %.2f | chunk ends %.2f | search %.2f | rows gathered %.2f | moment row %.2f | hand-over %.2f\n",
                                    0.0, (sp[1] - sp[0]) * 0.01, (sp[2] - sp[1]) * 0.01, (sp[3] - sp[2]) * 0.01, (sp[4] - sp[3]) * 0.01, (sp[5] - sp[4]) * 0.01, (sp[6] - sp[5]) * 0.01, (sp[7] - sp[6]) * 0.01, (sp[8] - sp[7]) * 0.01, (sp[9] - sp[8]) * 0.01);
             }
+            // (a one-block α = 1 stage of the fused proposal - proposal2_fused - stamps [30] and [31] in a profiling build only: of the first three
+            // figures only the sum means something in the library as built)
             fprintf(stderr, "[smcmi3]   decision + proposal: totals -> covariance, shuffle %lld | block matrices %lld | Cholesky + log det %lld | rest %lld\n",
                     pr[30] - pr[3], pr[31] - pr[30], pr[32] - pr[31], pr[4] - pr[32]);
+#ifdef SMCMI_PROF_CHOL
+            // (a profiling build's stamps inside the Cholesky wavefront, relative to the totals [3].  proposal2: [30] covariance published, [31] block
+            // matrices published, [33] rows loaded, [34] factor done, [32] stored and published.  proposal2_fused: [30] rows formed, [31] factor done,
+            // [32] stored and published; [33] and [34] are not written)
+            fprintf(stderr, "[smcmi3]   proposal stamps after the totals: decision [35] %lld | [30] %lld | [31] %lld | [33] %lld | [34] %lld | [32] %lld | [4] %lld\n",
+                    pr[35] - pr[3], pr[30] - pr[3], pr[31] - pr[3], pr[33] - pr[3], pr[34] - pr[3], pr[32] - pr[3], pr[4] - pr[3]);
+#endif
         }
         if (seg_launches > 0) {
             // the two hand-overs of that stage on the wall clock (10 ns ticks): when the workers' rows went out, what the gatherers did, when

@@ -38,7 +38,7 @@ constexpr int T1 = 512;           // threads of a correction block
 // whatever mix of launches and segments the profiled stage runs through:
 //   [PROF2_K1, +64)  K1's stamps: block 0 at +0.., the middle block at +32..   [PROF2_K2, +64)  K2's likewise (K2_STAMP below)
 //   [PROF2_CENSUS, + 3 PROF2_BLOCKS)   wall-clock start / end and CU of every block of a large-shard mutation launch (stage2b.hpp)
-//   [PROF2_SEG0, +64)   worker 0 of a segment: shader-clock stamps 1..9, the proposal's at +30..33 (K3_STAMP)
+//   [PROF2_SEG0, +64)   worker 0 of a segment: shader-clock stamps 1..9, the proposal's at +30..35 (K3_STAMP)
 //   [PROF2_SEL, +16)    ... its in-place selection (wall clock)
 //   [PROF2_GATH + 6 v, +6)  gatherer v's hand-over stamps, [PROF2_GPOLL + 4 v, +4) its polls    [PROF2_WORK + 4 b, +4)  worker b's hand-over stamps (wall clock)
 constexpr int PROF2_BLOCKS = 4096;
@@ -62,6 +62,14 @@ constexpr int PROF2_K1 = 0, PROF2_K2 = 64, PROF2_CENSUS = 128, PROF2_SEG0 = PROF
             (prof)[(slot)] = (long long)tt_;                                                                                   \
         }                                                                                                                     \
     } while (0)
+
+// ... inside wavefront 0 of proposal2_fused / of proposal2's Cholesky step: a profiling build alone has them (VARIANT_FLAGS=-DSMCMI_PROF_CHOL),
+// the library as built does not pay for them
+#ifdef SMCMI_PROF_CHOL
+#define K3_STAMP_FUSED(prof, slot) K3_STAMP_ANY(prof, slot)
+#else
+#define K3_STAMP_FUSED(prof, slot) do { } while (0)
+#endif
 
 struct Geo2 {
     long long N, n, nv;           // global / local / per-virtual-shard particles
@@ -1577,6 +1585,8 @@ __device__ inline void post2(int n, const Begin2 &bg, const Post2 &po, const Run
 // symmetrisation (smc_main.jl:457-465), random blocks (helpers.jl:215-260, Fisher-Yates on Philox), per block c²Σ_b = L Lᵀ
 // (mutation.jl:81, once per stage) - the arithmetic of k_prepare_mutation, by a block of TT >= 128 threads, results in LDS only.
 // Three barriers: [covariance | shuffle] -> [block matrices, marginal scales] -> [Cholesky, one wavefront per block] -> done.
+// (proposal2_fused - A1F_FUSE, α = 1 with one random block - has one: [rows of c²Σ from the totals, Cholesky, stores: wavefront 0 |
+// covariance, mean: wavefronts 1..6] -> done; the shuffle, the ball map and the zero fill of Ls ran in front of the wait for the totals.)
 struct Prop2 {                 // LDS pointers (k2_mutate carves them out of its dynamic LDS)
     double *covl, *A, *mean;
     int *bfree, *bptr, *fi;
@@ -1648,6 +1658,16 @@ constexpr int A1F_PRIOR = 32;  // Mut2Args::has_other carries the PRIOR_* bits a
 #define SMCMI_A1TARGET (A1F_BOUNDS | A1F_PRIOR)
 #endif
 static_assert(A1F_BOUNDS == (TGT_BOUNDS << 4) && A1F_PRIOR == (TGT_PRIOR << 4), "k2_mh_steps hands FAST >> 4 to mh_step");
+// ... and of the proposal itself with one random block (proposal2_fused below), in the same units:
+constexpr int A1F_FUSE = 64;   // nb == 1: the Cholesky wavefront forms its rows of c²Σ from the totals itself, one barrier where proposal2 has three
+#ifndef SMCMI_A1FUSE
+#define SMCMI_A1FUSE A1F_FUSE
+#endif
+// (measurement variants, VARIANT_FLAGS=-DSMCMI_FUSE_VARIANT=<bits>; 0 in the library as built.  2: nothing moves under the wait for the totals - ball
+// map and zero fill in proposal2_fused, behind a barrier of their own; 8: they do move, and proposal2 - which then leaves them out - builds the rest)
+#ifndef SMCMI_FUSE_VARIANT
+#define SMCMI_FUSE_VARIANT 0
+#endif
 
 // jx_pre: shuffle_partner() of lane (threadIdx.x & 63), valid in wavefront 1 (threads 64..127)
 // CHM: rows of the in-register Cholesky (12 serves n_para <= 12; 16 the wide kernels)
@@ -1657,6 +1677,8 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
                                  unsigned stage, const Prop2 &P, int *s_fail, int TT, int jx_pre, long long *prof = nullptr, long long *prof_any = nullptr) {
     const int t = threadIdx.x, da = d + 1;
     const double sw = T[0];
+    // (a one-block call from a unit with A1F_FUSE - a measurement variant's only: the caller has zero-filled Ls and stored ball under its wait)
+    [[maybe_unused]] const bool PRE = (FAST & A1F_FUSE) != 0 && nb == 1;
     if (t == 0) *s_fail = 0;
     for (int e = t; e < d * d; e += TT) {
         int a = e / d, b = e % d;
@@ -1670,7 +1692,7 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
         if (t >= 64 && t < 128) shuffle_trace(jx_pre, t - 64, nf, nb, P.bfree, P.bptr);      // wave 1 shuffles while the others finish the covariance
     }
     // (one block: every entry of Ls the Cholesky wavefront will not store is zero - nobody reads Ls between the previous MH step and the next)
-    if constexpr ((FAST & A1F_LS) != 0) { if (nb == 1) for (int e = t; e < d * d; e += TT) P.Ls[e] = 0.0; }
+    if constexpr ((FAST & A1F_LS) != 0) { if (nb == 1 && !PRE) for (int e = t; e < d * d; e += TT) P.Ls[e] = 0.0; }
     __syncthreads();
     K2_STAMP(prof, 4);
     K3_STAMP_ANY(prof_any, 0);
@@ -1679,7 +1701,7 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
     for (int i = t; i < nf; i += TT) {
         const int f = P.bfree[i];
         [[maybe_unused]] const double sff = sig(f, f);
-        P.ball[i] = P.fi[f];
+        if (!PRE) P.ball[i] = P.fi[f];
         if constexpr (!(FAST & A1F_NOMIX)) {
             P.mub[i] = P.mean[P.fi[f]];
             P.sdd[i] = sqrt(c * c * sff);
@@ -1707,6 +1729,7 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
             double r[CHM];
 #pragma unroll
             for (int k = 0; k < CHM; ++k) r[k] = (lane < db && k < db) ? P.A[off + lane * db + k] : 0.0;
+            K3_STAMP_FUSED(prof_any, 3);
             bool ok;
             // (the whole triangle in every lane's registers - no lane exchange, ~220 dependent FP64 operations - was measured: the same
             // 3.2 µs; a dependent FP64 operation costs ~16 cycles with one wavefront per SIMD, whichever way the ten columns are cut)
@@ -1714,6 +1737,7 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
                 if (db == d && d <= 10 && d >= 2) ok = chol_full_dispatch(r, d, lane);      // one block over all parameters: no per-column branches
                 else ok = chol_rows_in_regs<12, true>(r, db, lane);
             } else ok = chol_rows_in_regs<CHM, true>(r, db, lane);
+            K3_STAMP_FUSED(prof_any, 4);
             if (!ok && lane == 0) *s_fail = 1;
             if constexpr ((FAST & A1F_LS) != 0) {
                 if (nb == 1) {                      // row `lane` of L is column ball[lane] of the transposed, padded form: Ls[k][ball[lane]] = L[lane][k]
@@ -1743,6 +1767,86 @@ __device__ inline bool proposal2(const double *T, const double *shift, int d, in
     }
     __syncthreads();
     K2_STAMP(prof, 6);
+    K3_STAMP_ANY(prof_any, 2);
+    return *s_fail == 0;
+}
+
+// proposal2<CHM, FAST> at α = 1 with ONE random block (nb == 1; FAST has A1F_SHUF, A1F_NOMIX, A1F_LOGDET and A1F_LS), fused (A1F_FUSE): the
+// same values bit for bit - every entry is formed by the operations of proposal2 on the same operands in the same order - without the two
+// LDS round trips (covl, A) and two of the three barriers between the totals and the factor.
+//   The caller, in front of a barrier that lies in front of this call (its wait for the totals; `unpublished`: there was none - the stage at
+//   which a launch enters at its mutation - and it is paid here): shuffle_trace, P.ball[i] = P.fi[P.bfree[i]] (i < nf) by the wavefront that
+//   shuffled, P.Ls[0, d d) = 0 (nobody reads Ls between the previous MH step and this one).
+//   Wavefront 0: lane i < nf owns row i of A = c² R_fr: with a = ball[i], b = ball[k], lo <= hi the two ordered, v = T[p(lo, hi)] / sw -
+//   (T[lo + 1] / sw) (T[hi + 1] / sw) is covl[a d + b] AND covl[b d + a] of proposal2 (which swaps a <= b in before it forms either), so
+//   A[i][k] = c c ((v + v) / 2.0); a lane divides its own mean once and the others take it with bcast_lane (the same quotient of the same
+//   operands).  Rows go straight into the factorisation proposal2 dispatches to, then into Ls and Lraw as proposal2 stores them (the
+//   segment kernel reads only Lraw's diagonal - k2_mh_steps' log-determinant, A1F_LOGDET - and loff[0]: its selection, its exit and its leave
+//   note do not touch the proposal; storing the diagonal alone was measured and did not clear the bar).  No A in LDS on this path.
+//   Wavefronts 1 .. TT / 64 - 2: covl and mean, proposal2's expressions (off the chain: the export and the next stage's shift read them).
+//   The last wavefront is the caller's (post2).  One barrier.  s_fail: cleared by thread 0, set by lane 0 of the same wavefront.
+// Stamps (prof_any, thread 0): [0] the rows are formed, [1] the factor is done, [2] stored and published.
+// DMAX: the kernel's n_para (no column beyond it exists).  TT >= 192.
+template <int CHM, int DMAX>
+__device__ inline bool proposal2_fused(const double *T, const double *shift, int d, int nf, double c, const Prop2 &P, int *s_fail, int TT,
+                                       bool unpublished, long long *prof_any = nullptr) {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));                     // (a value as formed here: no address derived from it is kept in a register across the caller's stage loop)
+    const int da = d + 1;
+    const double sw = T[0];
+#if (SMCMI_FUSE_VARIANT) & 2
+    if (t >= 64 && t < 64 + nf) P.ball[t - 64] = P.fi[P.bfree[t - 64]];
+    for (int e = t; e < d * d; e += TT) P.Ls[e] = 0.0;
+    __syncthreads();
+#else
+    if (unpublished) __syncthreads();
+#endif
+    if (t < 64) {
+        const int lane = t, db = nf;
+        if (t == 0) *s_fail = 0;
+        const int a = lane < nf ? P.ball[lane] : 0;
+        const double ma = T[a + 1] / sw;
+        double r[CHM];
+#pragma unroll
+        for (int k = 0; k < CHM; ++k) {
+            r[k] = 0.0;
+            if (k < DMAX) {
+                const int b = __builtin_amdgcn_readlane(a, k);
+                const double mb = bcast_lane(ma, k);
+                const bool swap = a > b;
+                const int ra = (swap ? b : a) + 1, rb = (swap ? a : b) + 1;
+                const int p = ra * da - ra * (ra - 1) / 2 + (rb - ra);
+                const double v = T[p] / sw - (swap ? mb : ma) * (swap ? ma : mb);
+                r[k] = (lane < nf && k < nf) ? c * c * ((v + v) / 2.0) : 0.0;
+            }
+        }
+        K3_STAMP_FUSED(prof_any, 0);
+        bool ok;
+        if constexpr (CHM == 12) {
+            if (db == d && d <= 10 && d >= 2) ok = chol_full_dispatch(r, d, lane);      // (proposal2's dispatch)
+            else ok = chol_rows_in_regs<12, true>(r, db, lane);
+        } else ok = chol_rows_in_regs<CHM, true>(r, db, lane);
+        K3_STAMP_FUSED(prof_any, 1);
+        if (!ok && lane == 0) *s_fail = 1;
+#pragma unroll
+        for (int k = 0; k < CHM; ++k)
+            if (lane < db && k <= lane) P.Ls[k * d + a] = r[k];     // row `lane` of L is column ball[lane] of the transposed, padded form
+#pragma unroll
+        for (int k = 0; k < CHM; ++k)
+            if (lane < db && k < db) P.Lraw[lane * db + k] = k <= lane ? r[k] : 0.0;
+        if (lane == 0) P.loff[0] = 0;
+    } else if (t < TT - 64) {
+        const int TC = TT - 128;
+        for (int e = t - 64; e < d * d; e += TC) {
+            int a = e / d, b = e % d;
+            if (a > b) { const int tmp = a; a = b; b = tmp; }
+            const int ra = a + 1, rb = b + 1;
+            const int p = ra * da - ra * (ra - 1) / 2 + (rb - ra);
+            P.covl[e] = T[p] / sw - (T[a + 1] / sw) * (T[b + 1] / sw);
+        }
+        for (int a = t - 64; a < d; a += TC) P.mean[a] = shift[a] + T[a + 1] / sw;
+    }
+    __syncthreads();
     K3_STAMP_ANY(prof_any, 2);
     return *s_fail == 0;
 }

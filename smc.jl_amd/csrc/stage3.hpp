@@ -1272,9 +1272,10 @@ __device__ inline bool k3_rides(const RunParams &rp, const Seg3Args &sa, const P
 // the per-particle phases; it publishes two rows per hand-over and pays the serial phases and the hand-overs once.  A stage that must resample
 // does so in place (k3_select_two).
 // the A1F_* bits of an instantiation: the α = 1 fast path, and the MH step's target (A1F_BOUNDS, A1F_PRIOR) in the two-hand-over, one-handle,
-// one-chunk unit alone - the launcher (launch2.hpp launch_k3_seg) hands that one the model's PRIOR_* bits in Mut2Args::has_other
+// one-chunk unit alone - the launcher (launch2.hpp launch_k3_seg) hands that one the model's PRIOR_* bits in Mut2Args::has_other; the same
+// unit alone builds a one-block proposal fused (A1F_FUSE: stage2.hpp proposal2_fused)
 constexpr int k3_fast_bits(bool alpha1, bool ride, int ch, bool sys) {
-    return alpha1 ? ((SMCMI_A1FAST) | ((!ride && ch == 1 && !sys) ? (SMCMI_A1TARGET) : 0)) : 0;
+    return alpha1 ? ((SMCMI_A1FAST) | ((!ride && ch == 1 && !sys) ? ((SMCMI_A1TARGET) | (SMCMI_A1FUSE)) : 0)) : 0;
 }
 template <int D, bool ALPHA1, bool RIDE, int CH = 1, bool SYS = false>
 __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, DevState *st, Ctl2 *ctl, const ModelDev *md, Geo2 g, Mut2Args ma, Seg3Args sa, int nb, int nf) {
@@ -1685,6 +1686,19 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         // (α = 1: so is the shuffle itself - L.bfree and this stage's block pointers are idle since the previous stage's proposal; a selection
         // in between uses neither.  proposal2's first barrier publishes them)
         if constexpr ((FAST & A1F_SHUF) != 0) { if (tid >= 64 && tid < 128) shuffle_trace(jx_pre, tid - 64, nf, nb, L.bfree, L.bptr_s); }
+        // (A1F_FUSE, one random block: so are the map of the shuffled free set - by the wavefront that shuffled: each lane reads back its own
+        // entry - and the zero fill of Ls, idle since the previous stage's MH step, which its mutation row's barriers closed.  The barriers of
+        // the wait for the totals publish all three; the entered stage has no such wait and pays one in proposal2_fused)
+#if !((SMCMI_FUSE_VARIANT) & 2)
+        if constexpr ((FAST & A1F_FUSE) != 0) {
+            if (nb == 1) {
+                int t_ = tid;
+                asm volatile("" : "+v"(t_));                // (formed here: no address of these is kept in a register across the stage loop)
+                if (t_ >= 64 && t_ < 64 + nf) L.ball_raw[t_ - 64] = L.fi[L.bfree[t_ - 64]];
+                for (int e = t_; e < D * D; e += T3) L.Ls[e] = 0.0;
+            }
+        }
+#endif
         // ---- the V shard totals -> decision (smc_main.jl:427-455) -> proposal (smc_main.jl:457-465, helpers.jl:215-260, mutation.jl:81)
         if (!entered && !(RIDE && rides) && !(rows_two ? gather_totals<2>(sa.g_cm + K3_RPAR(n), g.V, MCM, -1, tag, sa.to, &s_to, s_tot, s_vt)
                                    : K3_TOTALS_CM(rows_direct ? sa.g_cm + K3_RPAR(n) : sa.gt_cm + K3_TPAR(n), tag))) { timed_out = true; break; }
@@ -1692,6 +1706,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         K3_WALL(sa.gprof, PROF2_WORK + 4 * blockIdx.x + 1);
         double ess = s_tot[0] * s_tot[0] / s_tot[1];
         int dec = entered ? 0 : decide2(s_a.bg, rp.threshold, rp.phi_rtol, s_tot[0], s_tot[1], &ess);
+        K3_STAMP_FUSED((sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr, 5);
 #ifndef SMCMI_K3_CH2
         if (__builtin_expect(dec == 1 && sa.sel != nullptr, 0)) {
             // ================= SELECTION inside the segment (k3_select_inside above): the particle goes through LDS - a call that took it in registers
@@ -1758,8 +1773,13 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         if (tid == T3 - 64) post2(n, s_a.bg, po, rp, s_tot[0], s_tot[1], ess, rs, &B.po);       // (the last wavefront: its logarithm runs beside the covariance and the shuffle of wavefronts 0 and 1)
         {
             Prop2 P{L.covl, L.Aw, L.mean_s, L.bfree, L.bptr_s, L.fi, L.Lraw, L.logdet_s, L.mub_raw, L.sdd_raw, L.sdn_raw, L.ball_raw, L.loff_s, L.Ls};
-            if (!proposal2<12, FAST>(s_tot + 2, po.shift, D, nf, nb, po.c * s_a.bg.cfac, ma.seed, (unsigned)n, P, &s_fail, T3, jx_pre, nullptr,
-                           (sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr)) {
+            // (A1F_FUSE and one random block - nb: a kernel argument, the same in every block - : proposal2_fused; `entered`: nothing has published
+            // what this stage's shuffle wavefront wrote)
+            if (!(((FAST & A1F_FUSE) != 0 && nb == 1 && !((SMCMI_FUSE_VARIANT) & 8))
+                      ? proposal2_fused<12, D>(s_tot + 2, po.shift, D, nf, po.c * s_a.bg.cfac, P, &s_fail, T3, entered,
+                                               (sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr)
+                      : proposal2<12, FAST>(s_tot + 2, po.shift, D, nf, nb, po.c * s_a.bg.cfac, ma.seed, (unsigned)n, P, &s_fail, T3, jx_pre, nullptr,
+                           (sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr))) {
                 // PosDefException aborts the run (mutation.jl:81).  The gatherers build no proposal and would wait for mutation rows that
                 // never come: the writer raises the waits' abort word (every bounded wait polls it), so they leave at once
                 if (writer && tid == 0) {
