@@ -149,7 +149,7 @@ __global__ void __launch_bounds__(ENS_T) kens_run(EnsArgs a) {
                     if (p < 0) continue;
                     const double e = en[p] - esh, w = wv[p];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) { const double v = w * exp((cand[k] - phi_n1) * e); acc[k] += v; acc[8 + k] += v * v; }
+                    for (int k = 0; k < 8; ++k) { const double v = weight_times(w, exp((cand[k] - phi_n1) * e)); acc[k] += v; acc[8 + k] += v * v; }
                 }
                 ens_totals<16>(acc, red, tot);
 #pragma unroll
@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(ENS_T) kens_run(EnsArgs a) {
             for (int q = 0; q < shape.per_thread; ++q) {
                 const long long p = ens_particle(shape, n, tid, q);
                 if (p < 0) continue;
-                const double e = en[p], v = wv[p] * exp(dphi * (e - esh));
+                const double e = en[p], v = weight_times(wv[p], exp(dphi * (e - esh)));      // (a row of weight 0 adds 0 whatever its energy: kernels.hpp)
                 wv[p] = v;
                 acc[0] += v; acc[1] += v * v;
                 if (hist) hist_w[(long long)(i - 1) * n + p] = exp(dphi * e);

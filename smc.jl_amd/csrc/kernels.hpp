@@ -653,6 +653,16 @@ __device__ inline double block_max(double v, double *smem, int nwaves) {
 __device__ inline double energy_base(double like_prev, double pw, double logp_old) {
     return pw == 0.0 ? like_prev : (pw == 1.0 ? 0.0 : log(exp(like_prev - logp_old + log(1.0 - pw)) + pw));
 }
+// Rows of weight 0.  The shift is the largest energy of the rows that still HAVE weight, so a row of weight 0 may lie any distance above it:
+// from 709.78 / δ on its shifted exp is +inf, 0 · inf is NaN and every sum of the stage with it; the history's inc · exp(δ e_shift) is inf · 0.
+// The reference's exponent is unshifted: such a row adds exactly 0 to every sum, keeps weight 0 and stores exp(δ e).  So a row of weight 0 takes
+// NO shift (row_shift / row_unshift: its inc is the reference's own exp(δ e), +inf where the reference's is) and its product is 0 whatever inc is
+// (weight_times) - selects, no branch and no second exp; rows with weight take the same operations on the same numbers as before, bit for bit.
+// A pass that stores nothing (the solver's) gives such a row the exponent 0 instead: 0 · exp(0) = 0 without a select per candidate (live_or_zero).
+__device__ inline double weight_times(double wi, double inc) { return wi == 0.0 ? 0.0 : wi * inc; }
+__device__ inline double row_shift(double wi, double esh) { return wi == 0.0 ? 0.0 : esh; }
+__device__ inline double row_unshift(double wi, double unshift) { return wi == 0.0 ? 1.0 : unshift; }
+__device__ inline double live_or_zero(double wi, double x) { return wi == 0.0 ? 0.0 : x; }
 __device__ inline double energy_or_ninf(double like, double like_prev, double w, bool live) {
     const double e = like - like_prev;
     return (live && w > 0.0 && fabs(e) < 1e300) ? e : -__builtin_inf();
@@ -709,7 +719,7 @@ __global__ void __launch_bounds__(TB) k_pass(CloudPtrs cl, DevState *st, const d
     block_chunk(cl.n, gridDim.x, blockIdx.x, beg, end);
     const double unshift = (FINAL && hist) ? exp((S.phi_n - phi_prev) * esh) : 1.0;     // history keeps the true exp(δ e)
     for (long long i = beg + threadIdx.x; i < end; i += TB) {
-        const double l = loglh[i] - esh, o = old[i], wi = w[i];
+        const double wi = w[i], l = loglh[i] - row_shift(wi, esh), o = old[i];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             if (!FINAL && k >= nv) continue;
@@ -718,12 +728,12 @@ __global__ void __launch_bounds__(TB) k_pass(CloudPtrs cl, DevState *st, const d
             if (!FINAL || pw == 0.0) inc = exp((phi_prev - phi) * o + (phi - phi_prev) * l);
             else if (pw == 1.0) inc = exp((phi - phi_prev) * l);
             else inc = exp((phi_prev - phi) * log(exp(o - logp_old + log(1.0 - pw)) + pw) + (phi - phi_prev) * l);
-            const double v = wi * inc;
+            const double v = weight_times(wi, inc);
             acc[k] += v;
             acc[K + k] += v * v;
             if (FINAL) {
                 w[i] = v;
-                if (hist) hist_w[(long long)stage_col * hist_ld + i] = inc * unshift;
+                if (hist) hist_w[(long long)stage_col * hist_ld + i] = inc * row_unshift(wi, unshift);
             }
         }
     }
@@ -773,7 +783,7 @@ __global__ void __launch_bounds__(TB) k_correct_moments(CloudPtrs cl, DevState *
     block_chunk(cl.n, gridDim.x, blockIdx.x, beg, end);
     const double unshift = hist ? exp((phi - phi_prev) * esh) : 1.0;                      // history keeps the true exp(δ e)
     for (long long i = beg + threadIdx.x; i < end; i += TB) {
-        const double l = loglh[i] - esh, o = old[i], wi = w[i];
+        const double wi = w[i], l = loglh[i] - row_shift(wi, esh), o = old[i];
         double xx[DA];
         xx[0] = 1.0;
 #pragma unroll
@@ -782,11 +792,11 @@ __global__ void __launch_bounds__(TB) k_correct_moments(CloudPtrs cl, DevState *
         if (pw == 0.0) inc = exp((phi_prev - phi) * o + (phi - phi_prev) * l);
         else if (pw == 1.0) inc = exp((phi - phi_prev) * l);
         else inc = exp((phi_prev - phi) * log(exp(o - logp_old + log(1.0 - pw)) + pw) + (phi - phi_prev) * l);
-        const double v = wi * inc;
+        const double v = weight_times(wi, inc);
         acc[0] += v;
         acc[1] += v * v;
         if (wt_out) wt_out[i] = v; else w[i] = v;        // spec stage: W stays intact until the prediction is verified
-        if (hist) hist_w[(long long)stage_col * hist_ld + i] = inc * unshift;
+        if (hist) hist_w[(long long)stage_col * hist_ld + i] = inc * row_unshift(wi, unshift);
         int q = 2;
 #pragma unroll
         for (int a = 0; a < DA; ++a) {

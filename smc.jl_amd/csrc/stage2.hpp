@@ -793,7 +793,7 @@ static __global__ void __launch_bounds__(T1) k2_pass(CloudPtrs cl, DevState *st,
     long long beg, end;
     vchunk(g, blockIdx.x / g.nb1, blockIdx.x % g.nb1, g.per1, beg, end);
     for (long long i = beg + threadIdx.x; i < end; i += T1) {
-        const double l = loglh[i] - esh, o = old[i], wi = w[i];
+        const double wi = w[i], l = live_or_zero(wi, loglh[i] - esh), o = live_or_zero(wi, old[i]);      // (a row of weight 0: 0 · exp(0), kernels.hpp)
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             if (k >= nv) continue;
@@ -923,7 +923,7 @@ __device__ inline void k2_cm_row(double (&acc)[((D + 1) * (D + 2) / 2 + 2 + 63) 
 template <int D, class XF>
 __device__ inline double k2_cm_weight(XF xf, const double *sh, double loglh, double old, double wi, double esh, double phi, double phi_prev, double pw,
                                       double logp_old, double (&xx)[D + 1], double *inc_out) {
-    const double l = loglh - esh, o = old;
+    const double l = loglh - row_shift(wi, esh), o = old;             // (a row of weight 0 takes no shift and adds 0: kernels.hpp)
     xx[0] = 1.0;
 #pragma unroll
     for (int a = 0; a < D; ++a) xx[a + 1] = xf(a) - sh[a];
@@ -932,7 +932,7 @@ __device__ inline double k2_cm_weight(XF xf, const double *sh, double loglh, dou
     else if (pw == 1.0) inc = exp((phi - phi_prev) * l);
     else inc = exp((phi_prev - phi) * log(exp(o - logp_old + log(1.0 - pw)) + pw) + (phi - phi_prev) * l);
     *inc_out = inc;
-    return wi * inc;
+    return weight_times(wi, inc);
 }
 // ... and its contribution to a correction block's accumulators: the sums of weighted_mean / weighted_cov about `sh`
 // (particle.jl:481-483, 526-529).
@@ -1063,9 +1063,10 @@ __global__ void __launch_bounds__(T1) k2_correct(CloudPtrs cl, DevState *st, Ctl
     // was tried: the 68 accumulator pairs leave no registers to carry it, the spills inside the loop cost more than the round trip)
     for (long long i = beg + threadIdx.x; i < end; i += T1) {
         double inc;
-        const double v = k2_cm_particle<D>(acc, [&](int a) { return col(cl, 0, a)[i]; }, sh, loglh[i], old[i], w[i], esh, phi, phi_prev, pw, logp_old, &inc);
+        const double wi = w[i];
+        const double v = k2_cm_particle<D>(acc, [&](int a) { return col(cl, 0, a)[i]; }, sh, loglh[i], old[i], wi, esh, phi, phi_prev, pw, logp_old, &inc);
         wt[i] = v;
-        if (hist) hist_w[(long long)(n - 1) * hist_ld + i] = inc * unshift;
+        if (hist) hist_w[(long long)(n - 1) * hist_ld + i] = inc * row_unshift(wi, unshift);
     }
     K2_STAMP(prof, 4);
     k2_cm_row<D>(acc, red, rows_cm + (long long)blockIdx.x * pad2(NPF), csum + blockIdx.x, TAIL && tail.tick != nullptr);
@@ -1077,10 +1078,11 @@ __global__ void __launch_bounds__(T1) k2_correct(CloudPtrs cl, DevState *st, Ctl
         const bool live = i < end;
         const long long il = live ? i : (end > beg ? end - 1 : 0);
         double xx[D + 1], inc;
-        double v = k2_cm_weight<D>([&](int a) { return col(cl, 0, a)[il]; }, sh, loglh[il], old[il], w[il], esh, phi, phi_prev, pw, logp_old, xx, &inc);
+        const double wi = w[il];
+        double v = k2_cm_weight<D>([&](int a) { return col(cl, 0, a)[il]; }, sh, loglh[il], old[il], wi, esh, phi, phi_prev, pw, logp_old, xx, &inc);
         if (live) {
             wt[i] = v;
-            if (hist) hist_w[(long long)(n - 1) * hist_ld + i] = inc * unshift;
+            if (hist) hist_w[(long long)(n - 1) * hist_ld + i] = inc * row_unshift(wi, unshift);
         } else v = 0.0;
         K2_STAMP(prof, 4);
         double *out = rows_cm + (long long)blockIdx.x * pad2(NPF);

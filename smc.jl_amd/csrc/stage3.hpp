@@ -1642,7 +1642,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
                     v = k2_cm_weight<D>([&](int a) { return x[a]; }, po.shift, like, like_prev, Wt, esh, phi, phi_prev, pw, logp_old, xx, &inc);
                     if (hist) {
                         const double unshift = exp((phi - phi_prev) * esh);
-                        sa.hist_w[(long long)(n - 1) * sa.hist_ld + i] = inc * unshift;
+                        sa.hist_w[(long long)(n - 1) * sa.hist_ld + i] = inc * row_unshift(Wt, unshift);
                     }
                 }
                 // (K3H_DEAD: a dead lane holds v == +0.0 - set above, k2_cm_weight ran under `live` only, and the entered stage, whose v is K1's,
@@ -1660,7 +1660,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
                     v = k2_cm_particle<D>(acc, [&](int a) { return x[a]; }, po.shift, like, like_prev, Wt, esh, phi, phi_prev, pw, logp_old, &inc);
                     if (hist) {
                         const double unshift = exp((phi - phi_prev) * esh);
-                        sa.hist_w[(long long)(n - 1) * sa.hist_ld + i] = inc * unshift;
+                        sa.hist_w[(long long)(n - 1) * sa.hist_ld + i] = inc * row_unshift(Wt, unshift);
                     }
                 }
                 k2_cm_row_f<D>(acc, red, [&](int idx, double val) { if (K3_HAS) gran_store(my_cm + idx * 2, val, tag); });

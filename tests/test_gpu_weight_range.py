@@ -26,6 +26,13 @@ Tolerances: ESS, log-MDD increment, normalised weights rtol 1e-11 at every offse
 |x| 2^-53 <= 8e-14 of argument rounding at |x| <= 745); incremental weights rtol 1e-11, atol 1e-300; adaptive ϕ rel 1e-9
 (test_solve_phi_vs_oracle); decisions, flags and shift_fallback_stage exact.
 
+Rows of weight 0 with the cloud's largest energy (wr.zero_high_cloud, δΔ = 0 .. 1e6 above the shift, fresh vehicle, fixed schedule and adaptive first
+correction, every row of PATHS): before the fix this case came with, 0 x exp(δΔ) = 0 x inf = NaN in every correction and solver pass and the history's
+inc x unshift was inf x 0 - measured on the parent's library (segments, launches, engine 1): SMCMI_ERR_NAN_ESS from δΔ = 745 on the fixed schedule (710 is
+still 708 above the live cloud's largest energy), SMCMI_ERR_BRACKET from δΔ = 700 on the adaptive first correction (the solver's candidates beyond the
+root); now such a row adds exactly 0 and stores the reference's exp(δ e) (kernels.hpp weight_times / row_shift): ESS 7.5e-16, W 7.6e-16, w 2.7e-14,
+log-MDD increment 2.5e-15, adaptive ϕ 2.2e-15 over all rows and δΔ.
+
 Measured on an MI355X (largest relative errors over all paths and cases): ESS 6.5e-16, W 4.6e-14, w 7.3e-14, log-MDD increment 5.5e-14, adaptive ϕ
 2.3e-15, at every offset; the lagged vehicle carries on at G = ±300 and falls back from ±350 on.  Before the fixes this file came with,
 measured on the continued vehicle's cloud (launches row: 20 480 particles of the 10-parameter Gaussian, stage 5 of the fixed schedule n_phi = 40,
@@ -85,6 +92,33 @@ def outlier_cloud(dD, n=N):
     return loglh, np.zeros(n), W
 
 
+# rows of weight 0 that hold the cloud's LARGEST energy, δΔ above the live rows' (wr.zero_high_cloud): the reference's ESS is the live rows' alone
+ZERO_DD = (0.0, 300.0, 700.0, 709.0, 710.0, 745.0, 800.0, 1e4, 1e6)
+ZERO_DS = 0.5                       # δ x spread of the live rows on the fixed schedule: ESS ≈ 0.78 of the live rows
+ZERO_ADAPT_S = 2.0                  # spread of the adaptive zero-weight clouds (the root then sits near δ = 0.14)
+
+
+def zero_cloud(dD, n=N):
+    loglh, W = wr.zero_high_cloud(n, DELTA, dD, ZERO_DS / DELTA, 47)
+    return loglh, np.zeros(n), W
+
+
+def zero_adaptive_delta(n=N):
+    """the reference's root on the adaptive zero-weight clouds (the rows of weight 0 and the common offset do not enter it)"""
+    loglh, W = wr.zero_high_cloud(n, 1.0, 0.0, ZERO_ADAPT_S, 48)
+    sched = (np.arange(ADAPT_KW["n_phi"]) / (ADAPT_KW["n_phi"] - 1.0)) ** ADAPT_KW["lam"]
+    return wr.solve_phi_ref(loglh, None, W, sched, 2, 0.0, 0.0, ADAPT_KW["tempering_target"], float(n), False)[0]
+
+
+def zero_adaptive_cloud(dD, delta_star, n=N):
+    loglh, W = wr.zero_high_cloud(n, delta_star, dD, ZERO_ADAPT_S, 48)
+    return loglh, np.zeros(n), W
+
+
+def zero_cases(kind="zero"):
+    return [dict(kind=kind, dD=dD, thr=0.5) for dD in ZERO_DD]
+
+
 def fresh_cases(offsets, pws=(0.0, 1.0, 0.3)):
     out = []
     for pw in pws:
@@ -113,6 +147,10 @@ def input_clouds():
         yield ("adaptive %r" % c, lambda c=c: adaptive_cloud(c["dB"], ds, c["pw"]) + (ds, 0.0, c["pw"], LOGP_OLD, c["thr"]))
     for c in outlier_cases():
         yield ("outlier %r" % c, lambda c=c: outlier_cloud(c["dD"]) + (DELTA, 0.0, 0.0, 0.0, c["thr"]))
+    dz = zero_adaptive_delta()
+    for c in zero_cases():
+        yield ("zero %r" % c, lambda c=c: zero_cloud(c["dD"]) + (DELTA, 0.0, 0.0, 0.0, c["thr"]))
+        yield ("zero, adaptive %r" % c, lambda c=c: zero_adaptive_cloud(c["dD"], dz) + (dz, 0.0, 0.0, 0.0, c["thr"]))
     n2 = PATHS["two_chunk_segments"][1]["n"]                            # the two-chunk row's clouds (n_para 10 as well; the wide row: n_para 12 < 50 * 10 / 40)
     ds2 = adaptive_delta(n2)
     for c in fresh_cases(wr.OFFSETS_REDUCED):
@@ -141,6 +179,7 @@ for r in range(shards):
     e.set_model(spec)
     es.append(e)
 ds = T.adaptive_delta(n) if any(c["kind"] == "adaptive" for c in cfg["cases"]) else None
+dz = T.zero_adaptive_delta(n) if any(c["kind"] == "zero_adaptive" for c in cfg["cases"]) else None
 
 def run(**kw):
     return eng.run_group(es, **kw) if shards > 1 else es[0].run(**kw)
@@ -166,13 +205,17 @@ for case in cfg["cases"]:
         for e in es:
             e.init_from_prior()
         kind = case["kind"]
-        if kind in ("fresh", "adaptive", "outlier"):
+        if kind in ("fresh", "adaptive", "outlier", "zero", "zero_adaptive"):
             k = 2
             P = download()
             if kind == "fresh":
                 loglh, old, W = T.fresh_cloud(case["dB"], case["dS"], case["pw"], case["weights"], n=n)
             elif kind == "adaptive":
                 loglh, old, W = T.adaptive_cloud(case["dB"], ds, case["pw"], n=n)
+            elif kind == "zero":
+                loglh, old, W = T.zero_cloud(case["dD"], n=n)
+            elif kind == "zero_adaptive":
+                loglh, old, W = T.zero_adaptive_cloud(case["dD"], dz, n=n)
             else:
                 loglh, old, W = T.outlier_cloud(case["dD"], n=n)
             pw = case.get("pw", 0.0)
@@ -230,6 +273,7 @@ for case in cfg["cases"]:
         else:
             o["W_rel"] = relmax(Wk, ref["W"], 1e-290)
             o["W_ok"] = bool(np.all(np.abs(Wk - ref["W"]) <= 1e-300 + T.RTOL * np.abs(ref["W"])))
+        o["dead_W_zero"] = bool(rec["resampled"][k - 1] or np.all(Wk[P[:, d + 4] == 0.0] == 0.0))      # (a row of weight 0 keeps weight 0)
         wk = w[:, k - 1]
         o["w_rel"] = relmax(wk, ref["w"], 1e-289)
         with np.errstate(invalid="ignore"):
@@ -281,6 +325,8 @@ def _check(res, fallback=0, segments=None, need_both=False):
             why.append("incremental weights off by %.3g" % o["w_rel"])
         if not o["logz_rel"] <= RTOL:
             why.append("log-MDD increment %r" % (o["logz"],))
+        if not o["dead_W_zero"]:
+            why.append("a row of weight 0 has weight")
         if not o["phi_rel"] <= (1e-9 if "phi" in o else 1e-14):
             why.append("phi off by %.3g" % o["phi_rel"])
         if fallback is not None and o["fallback"] != fallback:
@@ -413,6 +459,22 @@ def test_first_correction_on_knob_clouds_adaptive(path):
     # (an adaptive call's first correction is engine 2's launches on every row - see test_continued_stage...adaptive)
     cfg = dict(kw=ADAPT_KW, cases=cases, **over)
     _check(_run(cfg, env), fallback=0, segments=False if seg is False else None, need_both=True)
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+def test_rows_of_weight_zero_with_the_largest_energy_add_nothing_fixed_schedule(path):
+    """Fresh vehicle, δ = 1 / 8: rows of weight 0 whose energy lies δΔ = 0 .. 1e6 above the live cloud's largest (the shift).  The reference's
+    exponent is unshifted and finite, 0 x finite = 0: ESS, W, the log-MDD increment are the live rows' alone, those rows keep weight exactly 0,
+    their stored incremental weight is exp(δ e) = 1, nothing is NaN (_check: NaN fails every comparison)."""
+    env, over, seg = PATHS[path]
+    _check(_run(dict(kw=FRESH_KW, cases=zero_cases(), **over), env), fallback=0, segments=seg)
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+def test_rows_of_weight_zero_with_the_largest_energy_add_nothing_adaptive(path):
+    """The same on an adaptive call's first correction: the solver's passes see those rows at every candidate ϕ."""
+    env, over, seg = PATHS[path]
+    _check(_run(dict(kw=ADAPT_KW, cases=zero_cases("zero_adaptive"), **over), env), fallback=0, segments=False if seg is False else None)
 
 
 # δΔ up to which each path was measured right (engines 2 / 3: decide2 asks s2 >= 1e-290 and returns SMCMI_ERR_NAN_ESS beyond, from δΔ ≈ 340;

@@ -126,3 +126,32 @@ def test_the_restatements_factor_on_the_matrices_of_the_gpu_file_sets_the_step_t
     assert mr.chol_ref(S) is None
     with pytest.raises(Exception, match="positive definite"):
         orc.mixture_draw(np.zeros(12), np.zeros(12), S, T.FACTOR_C, 1.0, T.FACTOR_SEED, 0, T.FACTOR_STAGE, 0)
+
+
+def _measure_ensemble(i):
+    from tests import test_gpu_ensemble_range as E
+
+    name, make = list(E.moment_clouds())[i]
+    theta, W = make()
+    rm, rR = mr.weighted_moments(theta, W)
+    f = mr.chol_ref(rR)
+    return name, T.orc_error(theta, W, rm, rR), (f[2] if f is not None else -1.0)
+
+
+def test_the_restatement_on_the_ensemble_clouds(orc):
+    """The clouds of tests/test_gpu_ensemble_range.py (100 .. 8 192 particles, n_para 1 .. 10): every reference factor exists with pivots >= 1e-9
+    of the diagonal, every cloud is within TOL / 16 (TOL stays the cap of the per-cloud bound), and the restatement's largest error over them is
+    the figure recorded there as ENS_ORC_WORST."""
+    from concurrent.futures import ProcessPoolExecutor
+
+    from tests import test_gpu_ensemble_range as E
+
+    n_clouds = sum(1 for _ in E.moment_clouds())
+    with ProcessPoolExecutor(max_workers=8) as ex:
+        rows = list(ex.map(_measure_ensemble, range(n_clouds), chunksize=4))
+    worst, worst_name = max((e, name) for name, e, _ in rows)
+    print("the restatement's largest error over %d ensemble clouds: %.3g (%s); smallest pivot: %.3g" % (n_clouds, worst, worst_name, min(p for _, _, p in rows)))
+    for name, e_cov, pivot in rows:
+        assert e_cov <= T.TOL / 16.0, (name, e_cov)
+        assert pivot >= 1e-9, (name, pivot)
+    assert worst <= E.ENS_ORC_WORST <= 1.25 * worst, (worst, E.ENS_ORC_WORST)

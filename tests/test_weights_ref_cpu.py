@@ -2,7 +2,8 @@
 prior_weight forms), and against Python's `decimal` at 60 digits on small clouds with common offsets out to δ e = -2e7, where no
 FP64 restatement of the reference survives.  Also here, because it is a condition on inputs and not a measurement: every cloud of
 tests/test_gpu_weight_range.py keeps the reference's ESS above 50 n_para (a PosDef abort cannot be the cloud's fault) and the
-matrix holds both resample outcomes.
+matrix holds both resample outcomes.  The same for tests/test_gpu_ensemble_range.py, with the two helpers it rests on: chain_ref (the whole adaptive
+run of a frozen cloud) against the oracle's own loop, zero_high_cloud (rows of weight 0 with the largest energy) against the cloud without those rows.
 
 Measured (x86-64, longdouble = 80-bit): largest relative error against 60-digit decimal over the cases below - ESS 2.5e-16,
 normalised weights 2.1e-16, log-MDD increment 1.1e-16; the assertions ask 1e-13."""
@@ -169,3 +170,104 @@ def test_the_gpu_matrix_keeps_the_reference_ess_above_50_n_para_and_holds_both_r
         outcomes.add(r["resample"])
         n_cases += 1
     assert outcomes == {True, False} and n_cases >= 100, (outcomes, n_cases)
+
+
+# ------------------------------------------------------------------------------------------------ the frozen chain and the zero-weight structure
+def _sched30():
+    return (np.arange(30) / 29.0) ** 2.1
+
+
+def test_chain_ref_is_the_oracles_loop_on_a_frozen_cloud(orc):
+    """chain_ref against the restatement's own solve_adaptive_ϕ + correction, stage after stage, on a cloud the restatement's unshifted exp holds
+    (300 particles, spread 3): the same stages, the same schedule indices, ϕ to 1e-10, ESS / W / increments to 1e-12."""
+    n, d = 300, 2
+    e = wr.knob_cloud(n, 1.0, 0.0, 3.0, 43)[0]
+    sched = _sched30()
+    ch = wr.chain_ref(e, None, np.ones(n), sched, 0.9)
+    P = np.zeros((n, d + 5), order="F")
+    P[:, d], P[:, d + 4] = e, 1.0
+    j, phi_prop, phi, ess_prev, rl = 2, 0.0, 0.0, float(n), False
+    for s in ch:
+        assert s["j_in"] == j
+        phi_n, rl, j, phi_prop = orc.solve_adaptive_phi(P, ess_prev, sched, j, phi_prop, phi, 0.9, rl)[:4]
+        Q, inc, nw, ess, su = orc.correct(P, phi_n, phi, 0.0, 0.0)
+        assert s["phi"] == pytest.approx(phi_n, rel=1e-10) and (s["j"], s["phi_prop"]) == (j, phi_prop)
+        # (the sums at the restatement's ϕ: the reference evaluated there)
+        at = wr.correct_ref(e, None, P[:, d + 4], phi_n, phi)
+        assert at["ess"] == pytest.approx(ess, rel=1e-12) and at["logz_inc"] == pytest.approx(math.log(su / n), rel=1e-12, abs=1e-15)
+        np.testing.assert_allclose(at["W"], nw, rtol=1e-12)
+        np.testing.assert_allclose(s["w"], inc, rtol=1e-9)
+        P[:, d + 4], ess_prev, phi = nw, ess, phi_n
+    assert phi == 1.0 and ch[-1]["phi"] == 1.0
+    # evaluated at its own ϕ the chain repeats itself, bit for bit; and it refuses to resample
+    at = wr.chain_at(e, None, np.ones(n), [s["phi"] for s in ch])
+    assert [s["ess"] for s in at] == [s["ess"] for s in ch] and all(np.array_equal(a["W"], b["W"]) for a, b in zip(at, ch))
+    with pytest.raises(ValueError):
+        wr.chain_ref(e, None, np.ones(n), sched, 0.9, threshold_ratio=0.99)
+
+
+def test_frozen_chains_of_the_issue_table():
+    """knob_cloud(n, 1, 0, S, 43), n_phi = 30, λ = 2.1, never resampling (stages as a run counts them: the chain's + 1)"""
+    for n, S, target, stages, min_ess in ((1024, 8.0, 0.9, 15, 249.9), (1000, 8.0, 0.95, 29, 244.5), (300, 3.0, 0.9, 6, 181.0)):
+        ch = wr.chain_ref(wr.knob_cloud(n, 1.0, 0.0, S, 43)[0], None, np.ones(n), _sched30(), target)
+        print(n, S, target, len(ch) + 1, min(s["ess"] for s in ch), ch[0]["phi"])
+        assert len(ch) + 1 == stages and min(s["ess"] for s in ch) == pytest.approx(min_ess, abs=0.5)
+        if n == 1024:
+            assert ch[0]["phi"] == pytest.approx(0.14625, abs=1e-5)
+
+
+def test_zero_high_cloud_is_the_cloud_without_those_rows():
+    """Rows of weight 0 with the largest energy: the reference's ESS, W and increment are those of the cloud with the rows removed (the increment
+    corrected for N), their W is exactly 0, every output is finite - at every δΔ, far past the range of a shifted exp."""
+    assert list(wr.default_zero_rows(100)) == list(range(8)) + [97, 98, 99]
+    assert list(wr.default_zero_rows(1024)) == list(range(8)) + [255, 256, 1021, 1022, 1023]
+    assert wr.default_zero_rows(8192).size == 13 + 512 and set(range(1536, 2048)) <= set(wr.default_zero_rows(8192))
+    for n in (100, 1024, 8192):
+        rows = wr.default_zero_rows(n)
+        live = np.ones(n, dtype=bool)
+        live[rows] = False
+        for delta in (1.0, 0.125):
+            for dD in (0.0, 300.0, 700.0, 709.0, 710.0, 745.0, 800.0, 1e4, 1e6):
+                ll, W = wr.zero_high_cloud(n, delta, dD, 0.5 / delta, 46)
+                assert np.all(W[rows] == 0.0) and np.all(ll[rows] == 0.0) and W.sum() == pytest.approx(n) and np.all(W[live] > 0.0)
+                assert ll[live].mean() == pytest.approx(-dD / delta, abs=0.5 / delta)
+                r = wr.correct_ref(ll, None, W, 0.5 + delta, 0.5)
+                q = wr.correct_ref(ll[live], None, W[live], 0.5 + delta, 0.5)
+                nl = int(live.sum())
+                assert r["ess"] == pytest.approx(q["ess"], rel=1e-14)
+                np.testing.assert_allclose(r["W"][live], q["W"] * (n / nl), rtol=1e-14)
+                assert r["logz_inc"] == pytest.approx(q["logz_inc"] + math.log(nl / n), rel=1e-14, abs=1e-14)
+                assert np.all(r["W"][rows] == 0.0) and np.all(r["w"][rows] == 1.0)
+                assert np.isfinite(r["ess"]) and np.isfinite(r["logz_inc"]) and np.all(np.isfinite(r["W"])) and np.all(np.isfinite(r["w"]))
+
+
+def test_the_ensemble_matrix_keeps_the_reference_ess_above_50_n_para():
+    """Conditions on the inputs of tests/test_gpu_ensemble_range.py, with the helper alone: every one-stage cloud, and every stage of every frozen
+    chain; the chains have the shapes the file's docstring says (stage counts, the walk across solver passes, the walk off the schedule's end)."""
+    from tests import test_gpu_ensemble_range as T
+
+    n_cases, outcomes = 0, set()
+    for name, n_para, make in T.input_clouds():
+        loglh, old, W, thr = make()
+        r = wr.correct_ref(loglh, old, W, 1.0, 0.0, 0.0, 0.0, thr)
+        assert r["ess"] >= 50 * n_para, (name, r["ess"])
+        outcomes.add(r["resample"])
+        n_cases += 1
+    assert outcomes == {True, False} and n_cases >= 700, (outcomes, n_cases)
+    want = {"n1024_S8": (15, 249.9), "n1000_S8_target095": (29, 244.5), "n300_S3_walk_across_passes": (6, 181.4), "n257_S3": (6, 153.6), "n100_S3": (6, 59.1),
+            "n8192_S8_npara10": (15, 2051.8), "n8192_S200_many_small_steps": (44, 95.2)}
+    assert set(want) == set(T.FROZEN)
+    n_phi = T.ADAPT["n_phi"]
+    for name, f in T.FROZEN.items():
+        ch = T.frozen_chain(name)
+        ess = min(s["ess"] for s in ch)
+        print(name, len(ch) + 1, ess, [(s["j_in"], s["j"]) for s in ch[:3]], [(s["j_in"], s["j"]) for s in ch[-2:]])
+        assert ess >= 50 * f["d"], (name, ess)
+        assert (len(ch) + 1, pytest.approx(want[name][1], abs=0.06)) == (want[name][0], ess), (name, len(ch) + 1, ess)
+        # the last stage walks off the end of the schedule: j = n_phi + 1 on entry (no point left) or reached within the stage, and ϕ = 1
+        assert ch[-1]["phi"] == 1.0 and ch[-1]["j"] == n_phi + 1 and ch[-1]["phi_prop"] == 1.0
+    walk = T.frozen_chain("n300_S3_walk_across_passes")[0]
+    assert walk["j_in"] == 2 and walk["j"] >= 18                      # past the 8th and the 16th schedule point within one stage
+    assert any(s["j_in"] == n_phi + 1 for s in T.frozen_chain("n1024_S8"))
+    eq = T.frozen_chain("n1024_S8", "equal")
+    assert len(eq) == 1 and eq[0]["phi"] == 1.0 and eq[0]["ess"] == 1024.0

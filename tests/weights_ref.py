@@ -154,6 +154,62 @@ def knob_cloud(n, delta, dB, dS, seed, weights="ones"):
     return loglh, W
 
 
+def chain_ref(loglh, old_loglh, W, sched, target, threshold_ratio=0.0, phis=None, max_stages=400):
+    """The whole adaptive run of a FROZEN cloud (src/smc_main.jl:377-508 with every proposal rejected: the energies never change), as a chain
+    of solve_phi_ref + correct_ref until ϕ = 1, carrying j, ϕ_prop, ESS_prev and W as the reference loop does (start: j = 2, ϕ_prop = ϕ = 0,
+    ESS_prev = N, not resampled).  phis = None: ϕ_k is the reference's root.  phis given (a run's recorded ones, ϕ_2 first): every stage is
+    evaluated AT those values - a tolerance on ϕ then does not leak into the tolerances on the sums.  A frozen chain cannot resample (the
+    cloud would change): a stage whose ESS falls below threshold_ratio N raises ValueError; with threshold_ratio = 0 none does.
+    Returns one dict per stage: phi, ess, logz_inc, W (normalised, mean 1), w (incremental weights), resample (False), j_in / j (the schedule
+    index before / after the stage's walk, 1-based as the reference's), phi_prop."""
+    n = len(loglh)
+    Wc = np.asarray(W, dtype=np.float64).copy()
+    j, phi_prop, phi, ess_prev, rl = 2, 0.0, 0.0, float(n), False
+    out = []
+    while phi < 1.0:
+        if len(out) >= max_stages:
+            raise ValueError("the chain does not reach 1 within %d stages" % max_stages)
+        j_in = j
+        if phis is None:
+            phi_n, rl, j, phi_prop = solve_phi_ref(loglh, old_loglh, Wc, sched, j, phi_prop, phi, target, ess_prev, rl)
+        else:
+            phi_n = float(phis[len(out)])
+        r = correct_ref(loglh, old_loglh, Wc, phi_n, phi, 0.0, 0.0, threshold_ratio)
+        if r["resample"]:
+            raise ValueError("stage %d of a frozen chain would resample (ESS %r)" % (len(out) + 2, r["ess"]))
+        out.append(dict(phi=phi_n, ess=r["ess"], logz_inc=r["logz_inc"], W=r["W"], w=r["w"], resample=False, j_in=j_in, j=j, phi_prop=phi_prop))
+        Wc, ess_prev, phi = r["W"], r["ess"], phi_n
+    return out
+
+
+def chain_at(loglh, old_loglh, W, phis, threshold_ratio=0.0):
+    """chain_ref evaluated at given ϕ values (ϕ_2, ϕ_3, ... ending in 1): no solver"""
+    return chain_ref(loglh, old_loglh, W, None, None, threshold_ratio, phis=phis)
+
+
+def default_zero_rows(n):
+    """the first 8 rows, the two rows straddling index 255 / 256 (a wavefront and block boundary), the last 3 and - clouds of 4 096 and more -
+    one whole interior 512-chunk"""
+    rows = list(range(min(8, n))) + [r for r in (255, 256) if r < n] + list(range(max(n - 3, 0), n))
+    if n >= 4096:
+        rows += list(range(512 * 3, 512 * 4))
+    return np.unique(np.asarray(rows, dtype=np.int64))
+
+
+def zero_high_cloud(n, delta, dDelta, spread, seed, rows=None):
+    """Rows of weight 0 that hold the LARGEST energy of the cloud.  Live rows: e_i = -Δ + spread z_i with δ Δ = dDelta, z seeded standard
+    normal, weights normalised to sum n (ESS ≈ n_live exp(-(δ spread)²)).  Rows in `rows` (default_zero_rows): W = 0 and energy 0.  By the
+    reference's arithmetic those rows contribute exactly 0 (0 x a finite exp) and the cloud is the live rows alone.  Returns (loglh, W)."""
+    rng = np.random.default_rng(seed)
+    rows = default_zero_rows(n) if rows is None else np.asarray(rows, dtype=np.int64)
+    loglh = -(dDelta / delta) + spread * rng.standard_normal(n)
+    W = np.ones(n)
+    loglh[rows] = 0.0
+    W[rows] = 0.0
+    W *= n / W.sum()
+    return loglh, W
+
+
 def outlier_cloud(n, delta, dS, dDelta, seed):
     """knob_cloud at offset 0 with one more thing: particle n // 3 has the largest energy of the live cloud, above everyone else's by
     Δ (δ Δ = dDelta), and a negligible weight W = 1e-200.  By the reference's arithmetic it changes nothing."""
