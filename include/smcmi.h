@@ -225,9 +225,24 @@ int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const smcmi_devi
    callback on the other vintage is fine.  One launch per score: bounds gate (out-of-bounds proposals never reach the function), NaN -> -Inf
    and the evaluation count happen inside it, and the host reads nothing per MH step.  smcmi_callback_stats: calls = launches,
    evaluations = rows the function scored.  smcmi_callback_phases: `inside the callback` and the count wait are 0, the launches are under
-   `enqueueing`. */
+   `enqueueing`.
+   FUSED programs.  smcmi_program_compile_ex is smcmi_program_compile with flags (smcmi_program_compile is flags = 0; a bit other than
+   SMCMI_PROGRAM_FUSED: SMCMI_ERR_ARG).  SMCMI_PROGRAM_FUSED compiles the user's function into the engine's generic mutation kernel as
+   well: the code object holds the wrapper kernel and the kernel smcmi_program_mutate, the compile takes about half a second instead of a
+   tenth, and the source sees the library's own device headers and nothing else (-nostdinc -nostdinc++: an #include the library does not
+   supply is "file not found").  `options` reach the whole mutation kernel here, not the user's function alone, so more of them are
+   refused with SMCMI_ERR_ARG: include paths and forced includes (-I, -i..., --sysroot, -nostdinc...), floating-point contraction and
+   fast-math options, -U, and anything that names SMCMI_.  Registered at SMCMI_WHICH_NEW of a run that is not tempered (no likelihood of any kind at SMCMI_WHICH_OLD), such a program
+   mutates a stage in ONE launch - all MH steps and blocks, the function called on the proposal where the kernel holds it - with the bits
+   of the split path: same calls of the function on the same rows, same results.  Everywhere else (tempered updates, SMCMI_WHICH_OLD,
+   smcmi_init_from_prior, smcmi_initialize_likelihoods, smcmi_eval_cloud_callback) it runs as a plain program does, through the wrapper
+   kernel.  smcmi_callback_stats of a fused run: calls = launches = one per mutated stage, evaluations = rows the function scored.
+   smcmi_program_is_fused: *out = 1 for a program compiled with SMCMI_PROGRAM_FUSED, else 0. */
 typedef struct smcmi_program smcmi_program;
+#define SMCMI_PROGRAM_FUSED 1
 int smcmi_program_compile(const char *source, const char *entry, const char *options, smcmi_program **out);
+int smcmi_program_compile_ex(const char *source, const char *entry, const char *options, int32_t flags, smcmi_program **out);
+int smcmi_program_is_fused(const smcmi_program *p, int32_t *out);
 const char *smcmi_program_log(const smcmi_program *p);
 int smcmi_program_code(const smcmi_program *p, const void **code, int64_t *size);
 int smcmi_program_destroy(smcmi_program *p);

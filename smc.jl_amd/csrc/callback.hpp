@@ -256,6 +256,8 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
     if (int e = check_run_config(h, rc)) return e;
     const bool adaptive = !rc->use_fixed_schedule;
     const bool tempered = closure_lik(h, 1);
+    // a fused program (devcallback.hpp fused_mutation) may send its one launch ahead of the verdict: the kernel no-ops on st->done
+    const bool ahead = device_lik(h) && fused_mutation_serves(h, tempered) && sw().fused_ahead != 0;
     const bool on_device = device_lik(h);                 // the likelihood is a device function or a program (devcallback.hpp): no staging buffers, no copy streams
     if (int e = on_device ? ensure_dev_callback_buffers(h) : ensure_callback_buffers(h)) return e;
     if (pull_state(h)) return SMCMI_ERR_HIP;
@@ -296,6 +298,8 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
         stagepolicy::StallBook book(q.passes, q.passes, 8, base, false);
         bool first_enqueued = false;
         for (;;) {
+            // (ahead of the head's copy: the kernel writes nothing the head holds, and the host's wait below then covers it)
+            if (ahead) { if (int e = fused_mutation(h, false)) return e; }
             HIP_TRY(hipMemcpyAsync((char *)&head + head_off, (const char *)h->d_st + head_off, head_len, hipMemcpyDeviceToHost, h->stream));
             if (on_device) {
                 // (a device callback proposes once the verdict is known: its first wait is the count of in-bounds proposals anyway)
@@ -324,7 +328,8 @@ static int run_callback(smcmi_handle *h, const smcmi_run_config *rc, smcmi_resul
         }
         phase_ms[CBP_STAGE] += cb_now_ms() - ts0;
         if (done) break;                                 // ϕ = 1 was reached by the previous stage (its begin raised the flag), a pause, or an error
-        if (int e = host_mutation(h, rc, tempered, first_enqueued)) return e;
+        if (ahead) h->cb_calls += 1;                     // (the stage went ahead: the launch sent before its verdict was its mutation)
+        else if (int e = host_mutation(h, rc, tempered, first_enqueued)) return e;
         ++launched;
     }
     k_stage_begin<<<1, BT, 0, h->stream>>>(h->d_st, h->d_sched, h->d_acc_part, acc_nb, h->rec);

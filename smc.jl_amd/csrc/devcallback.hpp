@@ -196,11 +196,45 @@ static int prog_collect(smcmi_handle *h) {
     return 0;
 }
 
+// A FUSED program (include/smcmi.h SMCMI_PROGRAM_FUSED) at the new vintage of a run that is not tempered: the whole n_mh_steps x n_blocks loop
+// below is ONE launch of the program's own copy of the generic mutation kernel (fusedsrc.hpp smcmi_program_mutate = k_mutate<0, 1>'s body with
+// the user's function where mutate_generic scores a proposal), with the bits of the split path.  Anything at the old vintage - a family, a
+// callback, a program, a data prefix - keeps the split path.
+static inline bool fused_mutation_serves(const smcmi_handle *h, bool tempered) {
+    return h->prog[0].mutate != nullptr && !tempered && h->h_model.lik[1].family == SMCMI_LIK_NONE && h->h_model.lik_prefix == 0;
+}
+// The launch is launch_mutate's for the generic kernel (the staged proposal constants for n_para <= 13, h->nb_mut blocks of h->mut_T threads,
+// lds::mutate's bytes), and it leaves the energy sums and maxima exactly when the last accept launch of the split path does.  Like k_mutate it
+// is a no-op on a stage that did not go ahead.
+// count: the launch is a stage's mutation (false: sent ahead of the verdict - run_callback counts it once the stage went ahead).
+static int fused_mutation(smcmi_handle *h, bool count = true) {
+    const double t0 = cb_now_ms();
+    MutArgs ma{};
+    ma.seed = h->cfg.seed; ma.gid0 = h->cfg.gid0;
+    ma.stage_consts = h->d <= 13 ? 1 : 0;
+    if (h->cb_energy) { ma.esum = h->d_esum_part; ma.emax = h->d_emax_part; }
+    CloudPtrs cl = h->cl;
+    const DevState *st = h->d_st;
+    const ModelDev *md = h->d_model;
+    double *acc = h->d_acc_part;
+    int standalone = 0;
+    const double *data = h->d_prog_data[0], *par = h->d_prog_par[0];
+    long long rows = h->prog_rows[0], cols = h->prog_cols[0], n_par = h->prog_npar[0];
+    unsigned long long *evals = h->d_prog_evals;
+    void *args[] = {&cl, &st, &md, &ma, &acc, &standalone, &data, &rows, &cols, &par, &n_par, &evals};
+    const hipError_t e = (hipError_t)program::launch_mutate(h->prog[0], (unsigned)h->nb_mut, (unsigned)h->mut_T, h->mut_lds, args, (void *)h->stream);
+    h->dcbuf->phase_ms[CBP_ENQUEUE] += cb_now_ms() - t0;
+    if (e != hipSuccess) return set_err(SMCMI_ERR_HIP, std::string("launching the fused likelihood program: ") + hipGetErrorString(e));
+    if (count) h->cb_calls += 1;
+    return 0;
+}
+
 // host_mutation for a device callback: per MH step x block propose (k_mutate<1>, plain n x d proposals + their log-priors) -> the user's
 // function on the in-bounds ones (new data, and old data in a tempered update) -> accept (k_mutate<2>), in stream order on h->stream.
 static int device_mutation(smcmi_handle *h, const smcmi_run_config *rc, bool tempered) {
-    if (ensure_split_buffers(h)) return SMCMI_ERR_HIP;
     if (int e = ensure_dev_callback_buffers(h)) return e;
+    if (fused_mutation_serves(h, tempered)) return fused_mutation(h);
+    if (ensure_split_buffers(h)) return SMCMI_ERR_HIP;
     for (int step = 0; step < rc->n_mh_steps; ++step)
         for (int blk = 0; blk < rc->n_blocks; ++blk) {
             double t0 = cb_now_ms();

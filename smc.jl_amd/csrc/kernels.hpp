@@ -2171,6 +2171,28 @@ struct MutArgs {
     int stage_consts;          // k_mutate<0, 1>: the launch reserved sizeof(MutStage) + 64 bytes behind the per-thread vectors (n_para <= 13)
 };
 
+// A likelihood compiled at run time from HIP source, fused into the generic kernel (fusedsrc.hpp assemble / mutate_text): that translation unit defines
+// SMCMI_PROGRAM_ENTRY, the name of the user's function, before it includes this file.  mutate_generic and k_mutate's body then take one
+// more argument, the program's data and its evaluation tally, and the body is a device function the program's own kernel calls.  Without
+// the define - every translation unit of the library - the four macros expand to nothing or to the kernel's own head: the library compiles
+// from the same tokens with or without this block.
+#ifdef SMCMI_PROGRAM_ENTRY
+struct ProgHook {
+    const double *data;
+    long long rows, cols;
+    const double *par;
+    long long n_par;
+    unsigned long long scored;      // turns of the MH loop in which this wavefront's lanes called the function, lanes summed (every lane: the same)
+};
+#define SMCMI_PROG_PARAM , ProgHook &ph
+#define SMCMI_PROG_ARG , ph
+#define SMCMI_MUTATE_HEAD __device__ __forceinline__ void mutate_kernel_body
+#else
+#define SMCMI_PROG_PARAM
+#define SMCMI_PROG_ARG
+#define SMCMI_MUTATE_HEAD __global__ void __launch_bounds__(256, 1) k_mutate
+#endif
+
 // LS = 4 (lgss_kalman family only, MODE 0): FOUR lanes per particle - a 256-thread block carries 64 particles, the four lanes of a
 // quad run the per-particle part (draw, densities, prior, decision) redundantly on the same values (same counters -> same random
 // numbers; nothing to exchange) and share the Kalman filter (model.hpp kalman_lgss_quad).  Lane 0 of a quad stores the particle and
@@ -2195,7 +2217,7 @@ __device__ __forceinline__ void mutate_generic(const CloudPtrs &cl, const ModelD
                                                const unsigned stage, const double c_alpha, const double phi_n, const int nb, const int n_steps, const int d,
                                                const double *a_L, const double *a_mu, const double *a_sdd, const double *a_sdn, const double *a_logdet,
                                                const int *a_bptr, const int *a_ball, const int *a_loff, const ModelView &mv, double &like, double &lprior,
-                                               double &like_prev, double &accept) {
+                                               double &like_prev, double &accept SMCMI_PROG_PARAM) {
     if (live) {
         like = col(cl, src, d)[i]; lprior = col(cl, src, d + 1)[i]; like_prev = col(cl, src, d + 2)[i];
         load_columns(cl.buf[src], cl.n, i, d, th + tid, T);
@@ -2203,8 +2225,12 @@ __device__ __forceinline__ void mutate_generic(const CloudPtrs &cl, const ModelD
     }
     // lgss_kalman on both vintages with one thread per particle: the filter whose structure values travel through DPP operands
     // (model.hpp kalman_lgss_wave) - called by every lane, like the lane-split one.
+#ifdef SMCMI_PROGRAM_ENTRY
+    constexpr bool kalman_wave = false;      // (a program's kernel holds no device family: the host fuses only runs without one)
+#else
     const bool kalman_wave = LS == 1 && MODE == 0 && d == 13 && md->lik[0].family == SMCMI_LIK_LGSS_KALMAN &&
                              (md->lik[1].family == SMCMI_LIK_NONE || md->lik[1].family == SMCMI_LIK_LGSS_KALMAN);
+#endif
     auto TN = [&](int k) { return tn[k * T + tid]; };
     // proposal k of this particle in the MODE 1/2 buffer: proposals[k * p_ld + p_off]
     long long p_ld = cl.n, p_off = i;
@@ -2229,6 +2255,9 @@ __device__ __forceinline__ void mutate_generic(const CloudPtrs &cl, const ModelD
                 else if (t == 0) uniform_pair(ma.seed, pid, stage, rng_tag(P_MUT, 0xFFFFFu, 0), step_prob, u_dummy);
                 else uniform_pair(ma.seed, pid, stage, rng_tag(P_MUT, t - 1, 0), u_dummy, step_prob);
                 double q0 = 0.0, q1 = 0.0, prior_new = SMCMI_NEG_INF, like_new = SMCMI_NEG_INF, like_old_data = SMCMI_NEG_INF;
+#ifdef SMCMI_PROGRAM_ENTRY
+                bool prog_called = false;
+#endif
                 if (MODE != 2 && live) {
                     // ---- mvnormal_mixture_draw
                     double uc, unext;
@@ -2355,15 +2384,29 @@ __device__ __forceinline__ void mutate_generic(const CloudPtrs &cl, const ModelD
                     }
                 } else if (MODE != 2) {
                     if (live && inb) {
+#ifndef SMCMI_PROGRAM_ENTRY
                         if (md->lik_prefix > 0) {
                             // old data = a prefix of the data, same state-space structure: both log-likelihoods from one filter pass
                             double thv[13];
                             for (int k = 0; k < 13; ++k) thv[k] = TN(k);
                             const KalmanLL r = kalman_lgss2(thv, md->lik[0].data, md->lik[0].cols, md->lik_prefix, md->lik[0].aux, md->lik[0].par[0]);
                             like_new = r.ll; like_old_data = r.ll_mid;
-                        } else {
+                        } else
+#endif
+                        {
+#ifdef SMCMI_PROGRAM_ENTRY
+                            // the user's function on the proposal where it lies, column tid of tn: the rows the wrapper kernel's gate passes
+                            // (in bounds and a log-prior above -Inf), NaN -> -Inf, no old data; the others keep -Inf, -Inf as k_mutate<2> sets them
+                            if (prior_new != SMCMI_NEG_INF) {
+                                prog_called = true;
+                                like_new = SMCMI_PROGRAM_ENTRY(tn + tid, (long long)T, d, ph.data, ph.rows, ph.cols, ph.par, ph.n_par);
+                                if (like_new != like_new) like_new = SMCMI_NEG_INF;
+                                like_old_data = 0.0;
+                            }
+#else
                             like_new = loglik(md->lik[0], d, TN);
                             like_old_data = (md->lik[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik(md->lik[1], d, TN);
+#endif
                         }
                         if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
                     }
@@ -2380,6 +2423,9 @@ __device__ __forceinline__ void mutate_generic(const CloudPtrs &cl, const ModelD
                         if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
                     }
                 }
+#ifdef SMCMI_PROGRAM_ENTRY
+                ph.scored += (unsigned long long)__popcll(__ballot(prog_called));      // (the loops are uniform: every lane of the wavefront is here)
+#endif
                 const double eta = exp(phi_n * (like_new - like) + (1.0 - phi_n) * (like_old_data - like_prev) +
                                        (prior_new - lprior) + (q0 - q1));
                 if (!live) {}
@@ -2398,8 +2444,8 @@ __device__ __forceinline__ void mutate_generic(const CloudPtrs &cl, const ModelD
 }
 
 template <int MODE, int LS = 1>
-__global__ void __launch_bounds__(256, 1) k_mutate(CloudPtrs cl, const DevState *st, const ModelDev *md, MutArgs ma, double *acc_partials,
-                         int standalone) {
+SMCMI_MUTATE_HEAD(CloudPtrs cl, const DevState *st, const ModelDev *md, MutArgs ma, double *acc_partials,
+                         int standalone SMCMI_PROG_PARAM) {
     static_assert(LS == 1 || (LS == 4 && MODE == 0), "lane-split mutation: MODE 0 only");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!standalone && st->done) return;
@@ -2441,7 +2487,7 @@ __global__ void __launch_bounds__(256, 1) k_mutate(CloudPtrs cl, const DevState 
     const ModelView mv{d, staged ? S->fixed : md->fixed, staged ? S->prior_family : md->prior_family, staged ? S->lo : md->lo, staged ? S->hi : md->hi,
                        staged ? S->prior_a : md->prior_a, staged ? S->prior_b : md->prior_b, staged ? S->prior_k : md->prior_k};
     mutate_generic<MODE, LS>(cl, md, ma, th, tn, y, v, T, tid, quad_lane, i, live, src, pid, stage, c_alpha, phi_n, nb, n_steps, d, a_L, a_mu, a_sdd, a_sdn, a_logdet,
-                             a_bptr, a_ball, a_loff, mv, like, lprior, like_prev, accept);
+                             a_bptr, a_ball, a_loff, mv, like, lprior, like_prev, accept SMCMI_PROG_ARG);
     if (MODE == 1) return;
     double acc_val = 0.0;
     if (live && lead) {

@@ -20,6 +20,8 @@ constexpr double LOG2PI = 1.8378770664093454835606594728112;
 #define SMCMI_NEG_INF (-__builtin_huge_val())
 
 // host: per-parameter constant so the device never evaluates log() of a constant
+// (not for the run-time compiler, which has no host side: fusedsrc.hpp assemble)
+#ifndef __HIPCC_RTC__
 inline double prior_const_host(int fam, double a, double b) {
     switch (fam) {
     case SMCMI_PRIOR_NORMAL: return log(b);
@@ -31,6 +33,7 @@ inline double prior_const_host(int fam, double a, double b) {
     default: return NAN;
     }
 }
+#endif
 
 __device__ inline double prior_logpdf(int fam, double a, double b, double k, double x) {
     switch (fam) {
@@ -196,10 +199,12 @@ __device__ inline double logprior_normal_rb(const M &m, Th th) {
 }
 
 // host: family constant (same expression as the oracle so both sides share the libm value)
+#ifndef __HIPCC_RTC__
 inline double lik_const_host(int family, const double *par, int d) {
     if (family == SMCMI_LIK_GAUSS_ISO) return -0.5 * (double)d * log(2.0 * M_PI * par[0] * par[0]);
     return 0.0;
 }
+#endif
 
 // Linear-Gaussian state-space likelihood by the Kalman filter (build-defined model, no reference source).
 // n_s = 8 states, n_y = 3 observables, n_r = 3 shocks, d = 13 parameters: th[0..7] = ρ, th[8..10] = shock std σ, th[11] =

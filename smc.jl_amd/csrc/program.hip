@@ -12,6 +12,7 @@
 #include "../../include/smcmi.h"
 #include "program.hpp"
 #include "progsrc.hpp"
+#include "fusedsrc.hpp"
 
 static_assert(program::EVAL_SLOTS == progsrc::EVAL_SLOTS && program::EVAL_STRIDE == progsrc::EVAL_STRIDE, "the wrapper text and the host disagree about the counter");
 
@@ -71,25 +72,39 @@ std::string rtc_text(int code) {
 
 namespace program {
 
-int compile(const char *source, const char *entry, const char *options, smcmi_program **out, std::string *err) {
+int compile(const char *source, const char *entry, const char *options, int32_t flags, smcmi_program **out, std::string *err) {
     if (out) *out = nullptr;
     if (!source || !out) { *err = "smcmi_program_compile: null argument"; return SMCMI_ERR_ARG; }
+    if (flags & ~(int32_t)SMCMI_PROGRAM_FUSED) { *err = "smcmi_program_compile_ex: unknown flag bits"; return SMCMI_ERR_ARG; }
+    const bool fused = (flags & SMCMI_PROGRAM_FUSED) != 0;
     const char *ent = entry ? entry : progsrc::DEFAULT_ENTRY;
     if (!progsrc::valid_entry(ent)) { *err = "smcmi_program_compile: the entry is not a C identifier of at most 64 characters"; return SMCMI_ERR_ARG; }
     std::vector<std::string> extra;
     if (!progsrc::split_options(options, &extra, err)) return SMCMI_ERR_ARG;
+    if (fused && !fusedsrc::options_allowed(extra, err)) return SMCMI_ERR_ARG;
     if (!rtc_open(err)) return SMCMI_ERR_UNSUPPORTED;
     std::vector<std::string> opts = progsrc::base_options();
+    if (fused)
+        for (const std::string &o : fusedsrc::extra_options()) opts.push_back(o);
+#ifdef SMCMI_STRICT_FP
+    if (fused) opts.push_back("-DSMCMI_STRICT_FP");           // (the embedded kernels.hpp: the same contraction rule as this library's own)
+#endif
     opts.insert(opts.end(), extra.begin(), extra.end());
     std::vector<const char *> optv;
     for (const std::string &o : opts) optv.push_back(o.c_str());
-    const progsrc::Assembled text = progsrc::assemble(source, ent);
+    const progsrc::Assembled text = fused ? fusedsrc::assemble(source, ent) : progsrc::assemble(source, ent);
+    // a fused program reaches the project's device headers and the stand-ins of the system headers as named headers, and nothing else
+    std::vector<const char *> hdr_text, hdr_name;
+    if (fused)
+        for (const fusedsrc::Header &h : fusedsrc::header_table()) { hdr_name.push_back(h.name); hdr_text.push_back(h.text); }
 
     rtc_prog prog = nullptr;
-    int rc = g_rtc.CreateProgram(&prog, text.text.c_str(), progsrc::USER_FILE, 0, nullptr, nullptr);
+    int rc = g_rtc.CreateProgram(&prog, text.text.c_str(), progsrc::USER_FILE, (int)hdr_name.size(), fused ? hdr_text.data() : nullptr,
+                                 fused ? hdr_name.data() : nullptr);
     if (rc != 0 || !prog) { *err = "hiprtcCreateProgram: " + rtc_text(rc); return SMCMI_ERR_HIP; }
     smcmi_program *p = new smcmi_program();
     p->entry = ent;
+    p->fused = fused;
     rc = g_rtc.CompileProgram(prog, (int)optv.size(), optv.data());
     size_t len = 0;
     if (g_rtc.GetProgramLogSize(prog, &len) == 0 && len > 1) {
@@ -121,6 +136,15 @@ int load(const smcmi_program *p, Loaded *out, std::string *err) {
     hipFunction_t fn = nullptr;
     hipError_t e = hipModuleLoadData(&mod, p->code.data());
     if (e == hipSuccess) e = hipModuleGetFunction(&fn, mod, progsrc::KERNEL_NAME);
+    hipFunction_t mut = nullptr;
+    if (e == hipSuccess && p->fused) {
+        e = hipModuleGetFunction(&mut, mod, fusedsrc::MUTATE_NAME);
+        hipDeviceptr_t words = nullptr;
+        size_t bytes = 0;
+        if (e == hipSuccess) e = hipModuleGetGlobal(&words, &bytes, mod, fusedsrc::ABI_NAME);
+        if (e == hipSuccess && bytes != sizeof(out->abi)) e = hipErrorInvalidImage;
+        if (e == hipSuccess) e = hipMemcpyDtoH(out->abi, words, sizeof(out->abi));
+    }
     if (e != hipSuccess) {
         *err = std::string("loading the compiled likelihood: ") + hipGetErrorString(e);
         if (mod) (void)hipModuleUnload(mod);
@@ -129,12 +153,14 @@ int load(const smcmi_program *p, Loaded *out, std::string *err) {
     }
     out->module = (void *)mod;
     out->kernel = (void *)fn;
+    out->mutate = (void *)mut;
     return SMCMI_OK;
 }
 void unload(Loaded *l) {
     if (l->module) (void)hipModuleUnload((hipModule_t)l->module);
     l->module = nullptr;
     l->kernel = nullptr;
+    l->mutate = nullptr;
 }
 
 unsigned grid_for(long long n) {
@@ -145,6 +171,11 @@ int launch(const Loaded &l, const Args &a, void *stream) {
     Args v = a;
     void *args[] = {&v.theta, &v.gate, &v.n, &v.ld, &v.d, &v.data, &v.rows, &v.cols, &v.par, &v.n_par, &v.lik, &v.evals};
     return (int)hipModuleLaunchKernel((hipFunction_t)l.kernel, grid_for(a.n), 1, 1, progsrc::BLOCK, 1, 1, 0, (hipStream_t)stream, args, nullptr);
+}
+int launch_mutate(const Loaded &l, unsigned grid, unsigned block, size_t lds, void **args, void *stream) {
+    // (more than 64 KiB of dynamic LDS: the runtime has no call that raises the maximum of a MODULE's function - hipFuncSetAttribute takes a
+    // host function - and does not gate a module launch on it; the launch itself reports a request the device cannot serve)
+    return (int)hipModuleLaunchKernel((hipFunction_t)l.mutate, grid, 1, 1, block, 1, 1, (unsigned)lds, (hipStream_t)stream, args, nullptr);
 }
 
 }      // namespace program

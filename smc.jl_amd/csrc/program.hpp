@@ -8,6 +8,7 @@
 // a compiled program: host memory only, tied to no handle and no device
 struct smcmi_program {
     bool ok = false;                 // compiled: `code` holds a gfx950 code object with the wrapper kernel
+    bool fused = false;              // ... and the fused mutation kernel (SMCMI_PROGRAM_FUSED, csrc/fusedsrc.hpp)
     std::string entry;
     std::string log;                 // the compiler's log ("" when clean)
     std::vector<char> code;
@@ -16,11 +17,15 @@ struct smcmi_program {
 namespace program {
 
 // SMCMI_OK / _ERR_ARG / _ERR_UNSUPPORTED (no libhiprtc) / _ERR_COMPILE; *out is set for OK and ERR_COMPILE; `err` gets the message
-int compile(const char *source, const char *entry, const char *options, smcmi_program **out, std::string *err);
+// flags: 0 or SMCMI_PROGRAM_FUSED; any other bit is SMCMI_ERR_ARG
+int compile(const char *source, const char *entry, const char *options, int32_t flags, smcmi_program **out, std::string *err);
 
 // one program loaded on the current device: the handle's own module (hipModule_t / hipFunction_t behind void *)
+// (a fused program: also the fused mutation kernel, and the sizes its code object states for CloudPtrs, MutArgs, DevState and ModelDev -
+// the main translation unit, which has those structs, compares them with its own before it keeps the module)
 struct Loaded {
-    void *module = nullptr, *kernel = nullptr;
+    void *module = nullptr, *kernel = nullptr, *mutate = nullptr;
+    unsigned abi[4] = {0, 0, 0, 0};
 };
 int load(const smcmi_program *p, Loaded *out, std::string *err);       // SMCMI_OK / _ERR_HIP
 void unload(Loaded *l);
@@ -45,5 +50,8 @@ struct Args {
 };
 // enqueues the wrapper kernel on `stream` (a hipStream_t); returns the hipError_t as an int (0 = success)
 int launch(const Loaded &l, const Args &a, void *stream);
+// The fused mutation kernel on `stream`: grid x block threads, lds bytes of dynamic shared memory (the runtime does not gate a module's
+// launch at 64 KiB); `args` are the kernel's twelve arguments in order (devcallback.hpp fused_mutation).  Returns the hipError_t as an int.
+int launch_mutate(const Loaded &l, unsigned grid, unsigned block, size_t lds, void **args, void *stream);
 
 }      // namespace program

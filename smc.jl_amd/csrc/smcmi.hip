@@ -534,8 +534,18 @@ extern "C" int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const
 // ---- the same closure as HIP SOURCE, compiled at run time and called from a kernel of the engine's own (program.hip, progsrc.hpp)
 extern "C" int smcmi_program_compile(const char *source, const char *entry, const char *options, smcmi_program **out) {
     std::string err;
-    const int rc = program::compile(source, entry, options, out, &err);
+    const int rc = program::compile(source, entry, options, 0, out, &err);
     return rc ? set_err(rc, err) : 0;
+}
+extern "C" int smcmi_program_compile_ex(const char *source, const char *entry, const char *options, int32_t flags, smcmi_program **out) {
+    std::string err;
+    const int rc = program::compile(source, entry, options, flags, out, &err);
+    return rc ? set_err(rc, err) : 0;
+}
+extern "C" int smcmi_program_is_fused(const smcmi_program *p, int32_t *out) {
+    if (!p || !out) return set_err(SMCMI_ERR_ARG, "smcmi_program_is_fused: null argument");
+    *out = p->fused ? 1 : 0;
+    return 0;
 }
 extern "C" const char *smcmi_program_log(const smcmi_program *p) { return p ? p->log.c_str() : ""; }
 extern "C" int smcmi_program_code(const smcmi_program *p, const void **code, int64_t *size) {
@@ -560,6 +570,12 @@ extern "C" int smcmi_set_likelihood_program(smcmi_handle *h, int32_t which, cons
     if (p) {
         std::string err;
         if (int rc = program::load(p, &mod, &err)) return set_err(rc, err);
+        // a fused kernel takes CloudPtrs / MutArgs by value and reads DevState / ModelDev: its code object must lay them out as this library does
+        const unsigned abi[4] = {(unsigned)sizeof(CloudPtrs), (unsigned)sizeof(MutArgs), (unsigned)sizeof(DevState), (unsigned)sizeof(ModelDev)};
+        if (mod.mutate && memcmp(abi, mod.abi, sizeof(abi)) != 0) {
+            program::unload(&mod);
+            return set_err(SMCMI_ERR_STATE, "the fused program was compiled against other struct layouts than this library's");
+        }
         bool ok = h->d_prog_evals || dmalloc(h->mem, &h->d_prog_evals, (size_t)program::EVAL_WORDS) == 0;
         if (ok && rows * cols > 0) ok = dmalloc(h->mem, &d_data, (size_t)(rows * cols)) == 0 && hipMemcpy(d_data, data, sizeof(double) * rows * cols, hipMemcpyHostToDevice) == hipSuccess;
         if (ok && n_par > 0) ok = dmalloc(h->mem, &d_par, (size_t)n_par) == 0 && hipMemcpy(d_par, par, sizeof(double) * n_par, hipMemcpyHostToDevice) == hipSuccess;

@@ -32,6 +32,7 @@ struct Switches {
     int kalman_lanes = 0;           // SMCMI_KALMAN_LANES: 1 / 4 lanes per particle, 0 = by cloud size
     int no_lik_prefix = 0;          // SMCMI_NO_LIK_PREFIX: 1 = two filter passes
     int cb_chunks = 0;              // SMCMI_CB_CHUNKS: chunks per batch, 0 = by batch size
+    int fused_ahead = 0;            // SMCMI_FUSED_AHEAD: 1 = a fused program's mutation launch goes out before the stage's verdict is read
     // ---- diagnostics
     int trace = 0;                  // SMCMI_TRACE
     OptInt prof2;                   // SMCMI_PROF2=<stage>
@@ -52,6 +53,7 @@ struct Switches {
         if (const char *v = getenv("SMCMI_RNG_AHEAD_PART")) s.rng_ahead_part = atoll(v);
         if (const char *v = getenv("SMCMI_RESAMPLE_EXCHANGE")) s.resample_allgather = std::string(v) == "allgather";
         integer("SMCMI_KALMAN_LANES", &s.kalman_lanes); integer("SMCMI_NO_LIK_PREFIX", &s.no_lik_prefix); integer("SMCMI_CB_CHUNKS", &s.cb_chunks);
+        integer("SMCMI_FUSED_AHEAD", &s.fused_ahead);
         integer("SMCMI_TRACE", &s.trace); opt("SMCMI_PROF2", &s.prof2); integer("SMCMI_POISON_ALLOC", &s.poison_alloc);
         if (const char *v = getenv("SMCMI_RCCL_PATH")) s.rccl_path = v;
         s.read_per_run();

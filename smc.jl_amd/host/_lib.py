@@ -24,6 +24,7 @@ RESAMPLE = {"systematic": 0, "multinomial": 1, "polyalgo": 1}
 ERRORS = {-1: "ARG", -2: "HIP", -3: "NAN_ESS", -4: "POSDEF", -5: "CAPACITY", -6: "BRACKET", -7: "UNSUPPORTED", -8: "STATE", -9: "CALLBACK", -10: "TIMEOUT", -11: "COMPILE"}
 
 ERR_COMPILE = -11
+PROGRAM_FUSED = 1          # smcmi_program_compile_ex flag: the likelihood is also compiled into the generic mutation kernel
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -102,6 +103,8 @@ SYMBOLS = [
     ("smcmi_set_likelihood_device", C.c_int, [_H, C.c_int32, C.c_void_p]),      # const smcmi_device_likelihood * (C.byref(DeviceLik) or None)
     # likelihoods compiled at run time from HIP source: smcmi_program * is an opaque pointer, the code object a (pointer, size) pair
     ("smcmi_program_compile", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("smcmi_program_compile_ex", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    ("smcmi_program_is_fused", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     ("smcmi_program_log", C.c_char_p, [C.c_void_p]),
     ("smcmi_program_code", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), lp]),
     ("smcmi_program_destroy", C.c_int, [C.c_void_p]),

@@ -208,18 +208,19 @@ class HIPLikelihood:
     `source` defines `__device__ double loglik(const double *theta, long long ld, int d, const double *data, long long rows,
     long long cols, const double *par, long long n_par)` with theta[j * ld] parameter j of the proposal.  smc(HIPLikelihood(source),
     parameters, data, ...) hands `data` (2-d, column-major on the device) and `par` to the function and routes it through
-    Engine.set_likelihood_program: one launch per MH step x block, nothing read by the host."""
+    Engine.set_likelihood_program: one launch per MH step x block, nothing read by the host.  fused=True compiles the function into the
+    generic mutation kernel as well (a compile of about half a second): a run that is not tempered then mutates a stage in one launch, same bits."""
 
-    def __init__(self, source, par=None, entry="loglik", options=None):
+    def __init__(self, source, par=None, entry="loglik", options=None, fused=False):
         if not isinstance(source, (str, bytes)):
             raise TypeError("HIPLikelihood takes the likelihood's HIP source as text")
-        self.source, self.par, self.entry, self.options = source, par, entry, options
+        self.source, self.par, self.entry, self.options, self.fused = source, par, entry, options, bool(fused)
         self._program = None
 
     def program(self):
         """the compiled program (compiled on first use; a compiler error raises CompileError with the log)"""
         if self._program is None:
-            self._program = Engine.compile_program(self.source, entry=self.entry, options=self.options)
+            self._program = Engine.compile_program(self.source, entry=self.entry, options=self.options, fused=self.fused)
         return self._program
 
 

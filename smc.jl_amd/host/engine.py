@@ -33,13 +33,18 @@ class CompileError(_lib.SMCMIError):
 
 
 class Program:
-    """A likelihood compiled from HIP source (include/smcmi.h smcmi_program_*): host memory only, tied to no engine and no device."""
+    """A likelihood compiled from HIP source (include/smcmi.h smcmi_program_*): host memory only, tied to no engine and no device.
+    fused=True (SMCMI_PROGRAM_FUSED): the function is compiled into the generic mutation kernel as well - one launch per stage where the
+    run allows it, a compile of about half a second."""
 
-    def __init__(self, source, entry="loglik", options=None):
+    def __init__(self, source, entry="loglik", options=None, fused=False):
         L = _lib.lib()
         self._L, self._p = L, C.c_void_p()
         enc = lambda s: None if s is None else s.encode() if isinstance(s, str) else bytes(s)
-        rc = L.smcmi_program_compile(enc(source), enc(entry), enc(options), C.byref(self._p))
+        if fused:
+            rc = L.smcmi_program_compile_ex(enc(source), enc(entry), enc(options), _lib.PROGRAM_FUSED, C.byref(self._p))
+        else:
+            rc = L.smcmi_program_compile(enc(source), enc(entry), enc(options), C.byref(self._p))
         if rc != 0:
             msg = L.smcmi_last_error().decode()
             log = L.smcmi_program_log(self._p).decode(errors="replace") if self._p else ""
@@ -51,6 +56,12 @@ class Program:
     @property
     def log(self):
         return self._L.smcmi_program_log(self._p).decode(errors="replace")
+
+    @property
+    def fused(self):
+        v = C.c_int32()
+        check(self._L.smcmi_program_is_fused(self._p, C.byref(v)))
+        return bool(v.value)
 
     @property
     def code(self):
@@ -181,22 +192,24 @@ class Engine:
         check(self._L.smcmi_set_likelihood_device(self._h, which, C.byref(st)))
 
     @staticmethod
-    def compile_program(source, entry="loglik", options=None):
+    def compile_program(source, entry="loglik", options=None, fused=False):
         """Compile a likelihood given as HIP source (smcmi_program_compile; needs no GPU and no engine): the source defines
         `__device__ double loglik(const double *theta, long long ld, int d, const double *data, long long rows, long long cols,
         const double *par, long long n_par)` with theta[j * ld] parameter j of the proposal.  Returns a Program; a compiler error
-        raises CompileError, whose .log has the compiler's messages with the line numbers of `source` (likelihood.hip:<line>)."""
-        return Program(source, entry=entry, options=options)
+        raises CompileError, whose .log has the compiler's messages with the line numbers of `source` (likelihood.hip:<line>).
+        fused=True (smcmi_program_compile_ex, SMCMI_PROGRAM_FUSED): the function is also compiled into the generic mutation kernel - a
+        run that is not tempered then mutates a stage in one launch, with the bits of the split path."""
+        return Program(source, entry=entry, options=options, fused=fused)
 
-    def set_likelihood_program(self, program_or_source, data=None, par=None, which=0):
-        """Register a compiled likelihood (smcmi_set_likelihood_program): a Program, or source text that is compiled first.  data (2-d,
-        passed column-major) and par become the function's `data` / `par` on the device.  None unregisters.  The handle keeps its own
-        module: the Program may be closed right away."""
+    def set_likelihood_program(self, program_or_source, data=None, par=None, which=0, fused=False):
+        """Register a compiled likelihood (smcmi_set_likelihood_program): a Program, or source text that is compiled first (fused: as
+        compile_program; a Program keeps what it was compiled as).  data (2-d, passed column-major) and par become the function's
+        `data` / `par` on the device.  None unregisters.  The handle keeps its own module: the Program may be closed right away."""
         if program_or_source is None:
             check(self._L.smcmi_set_likelihood_program(self._h, which, None, None, 0, 0, None, 0))
             return
         own = not isinstance(program_or_source, Program)
-        prog = Program(program_or_source) if own else program_or_source
+        prog = Program(program_or_source, fused=fused) if own else program_or_source
         try:
             par = _f64(() if par is None else par).ravel()
             data = None if data is None else np.asfortranarray(np.atleast_2d(np.asarray(data, dtype=np.float64)))

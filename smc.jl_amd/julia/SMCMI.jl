@@ -155,14 +155,17 @@ lik_aux(::Any) = zeros(0, 0)
 #                            const double *par, long long n_par)
 # with theta[j * ld] parameter j (0-based) of the proposal; `data` is the matrix given to smc (column-major), `par` the vector below.
 # smc(HIPLikelihood(source; par = [...]), parameters, data; kwargs...) runs it; old_loglikelihood may be another HIPLikelihood.
+# fused = true (SMCMI_PROGRAM_FUSED): the function is compiled into the generic mutation kernel as well - a compile of about half a second, and a run
+# that is not tempered mutates a stage in one launch, with the bits of the split path.
 struct HIPLikelihood
     source::String
     par::Vector{Float64}
     entry::String
     options::Union{Nothing, String}
+    fused::Bool
 end
-HIPLikelihood(source::AbstractString; par = Float64[], entry = "loglik", options = nothing) =
-    HIPLikelihood(String(source), Float64[x for x in par], String(entry), options)
+HIPLikelihood(source::AbstractString; par = Float64[], entry = "loglik", options = nothing, fused = false) =
+    HIPLikelihood(String(source), Float64[x for x in par], String(entry), options, Bool(fused))
 const Program = Ptr{Cvoid}                                   # smcmi_program *
 struct CompileError <: Exception
     code::Int
@@ -172,7 +175,7 @@ Base.showerror(io::IO, e::CompileError) = print(io, "SMCMI: the likelihood sourc
 function compile_program(lik::HIPLikelihood)
     p = Ref{Program}(C_NULL)
     opts = lik.options === nothing ? Cstring(C_NULL) : lik.options
-    rc = ccall((:smcmi_program_compile, LIB), Cint, (Cstring, Cstring, Cstring, Ref{Program}), lik.source, lik.entry, opts, p)
+    rc = ccall((:smcmi_program_compile_ex, LIB), Cint, (Cstring, Cstring, Cstring, Int32, Ref{Program}), lik.source, lik.entry, opts, Int32(lik.fused ? 1 : 0), p)
     if rc != 0
         log = p[] == C_NULL ? "" : unsafe_string(ccall((:smcmi_program_log, LIB), Cstring, (Ptr{Cvoid},), p[]))
         p[] == C_NULL || ccall((:smcmi_program_destroy, LIB), Cint, (Ptr{Cvoid},), p[])
