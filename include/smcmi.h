@@ -221,7 +221,7 @@ int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const smcmi_devi
    keeps its own module: the program may be destroyed right after the call and registered on any number of handles and devices.
    A program is served wherever a device callback is (smcmi_run, smcmi_run_group, smcmi_init_from_prior, smcmi_initialize_likelihoods,
    smcmi_eval_cloud_callback, tempered updates through which = SMCMI_WHICH_OLD, pause / continue), refused where one is (smcmi_run_sharded,
-   smcmi_run_ensemble: SMCMI_ERR_UNSUPPORTED), and a host callback on the other vintage gives SMCMI_ERR_STATE from the run; a device
+   smcmi_run_ensemble - unless it was compiled for ensembles, below: SMCMI_ERR_UNSUPPORTED), and a host callback on the other vintage gives SMCMI_ERR_STATE from the run; a device
    callback on the other vintage is fine.  One launch per score: bounds gate (out-of-bounds proposals never reach the function), NaN -> -Inf
    and the evaluation count happen inside it, and the host reads nothing per MH step.  smcmi_callback_stats: calls = launches,
    evaluations = rows the function scored.  smcmi_callback_phases: `inside the callback` and the count wait are 0, the launches are under
@@ -237,12 +237,24 @@ int smcmi_set_likelihood_device(smcmi_handle *h, int32_t which, const smcmi_devi
    of the split path: same calls of the function on the same rows, same results.  Everywhere else (tempered updates, SMCMI_WHICH_OLD,
    smcmi_init_from_prior, smcmi_initialize_likelihoods, smcmi_eval_cloud_callback) it runs as a plain program does, through the wrapper
    kernel.  smcmi_callback_stats of a fused run: calls = launches = one per mutated stage, evaluations = rows the function scored.
-   smcmi_program_is_fused: *out = 1 for a program compiled with SMCMI_PROGRAM_FUSED, else 0. */
+   smcmi_program_is_fused: *out = 1 for a program compiled with SMCMI_PROGRAM_FUSED, else 0.
+   ENSEMBLE programs.  smcmi_program_compile_ensemble compiles the user's function into the ensemble kernel for n_para parameters (1..10,
+   anything else: SMCMI_ERR_ARG; the kernel is a template over n_para, so the compile has to know it): the code object holds the wrapper
+   kernel and the kernel smcmi_program_ensemble.  Options, their refusals, the header isolation and the log's line numbers are those of a
+   fused compile; the compile takes a few seconds.  Registered at SMCMI_WHICH_NEW on every member, with each member's own data and par (any
+   rows, cols and n_par: data vintages side by side), such a program runs through smcmi_run_ensemble: ONE launch for all members' whole
+   runs, the function called on the proposal where the kernel holds it - theta is a private array, ld = 1, d = n_para - under the rules of
+   the split path: only for in-bounds proposals with a log-prior above -Inf of live particles, NaN taken as -Inf, -Inf taking the prior with
+   it.  Everywhere else (smcmi_run, smcmi_init_from_prior, smcmi_initialize_likelihoods, smcmi_eval_cloud_callback, SMCMI_WHICH_OLD) it runs
+   as a plain program does, through the wrapper kernel.  smcmi_callback_stats of a member after smcmi_run_ensemble: calls = 1, evaluations =
+   rows its workgroup scored.  smcmi_program_ensemble_para: *out = the n_para of an ensemble program, 0 for any other. */
 typedef struct smcmi_program smcmi_program;
 #define SMCMI_PROGRAM_FUSED 1
 int smcmi_program_compile(const char *source, const char *entry, const char *options, smcmi_program **out);
 int smcmi_program_compile_ex(const char *source, const char *entry, const char *options, int32_t flags, smcmi_program **out);
 int smcmi_program_is_fused(const smcmi_program *p, int32_t *out);
+int smcmi_program_compile_ensemble(const char *source, const char *entry, const char *options, int32_t n_para, smcmi_program **out);
+int smcmi_program_ensemble_para(const smcmi_program *p, int32_t *out);
 const char *smcmi_program_log(const smcmi_program *p);
 int smcmi_program_code(const smcmi_program *p, const void **code, int64_t *size);
 int smcmi_program_destroy(smcmi_program *p);
@@ -378,7 +390,7 @@ int smcmi_mailbox_import(smcmi_handle *h, int32_t rank, int32_t world, const uin
 int smcmi_mailbox_selftest(smcmi_handle *h, int32_t rank, int32_t world, int32_t rounds, int32_t *errors_out);
 int smcmi_mailbox_active(smcmi_handle *h, int32_t *active_out);   /* 1: the last sharded run handed its per-stage sums over through the mailbox */
 int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, smcmi_result *res);
-/* ---- an ensemble of small runs in ONE launch (csrc/runens.hpp, csrc/enskernel.hpp) ----------------------------------------------
+/* ---- an ensemble of small runs in ONE launch (csrc/runens.hpp, csrc/ensbody.hpp) -------------------------------------------------
    The reference's workloads are small (n_parts defaults to 5 000, its examples use 1 000) and are run many times over: seeds, data
    vintages, model variants.  smcmi_run_ensemble runs n such runs at once, ONE WORKGROUP PER RUN: member k runs the whole loop of
    src/smc_main.jl:377-508 under `rc` from its own cloud with its own seed, on the library's Philox contract, until phi = 1.  Members
@@ -388,14 +400,19 @@ int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, sm
    n_parts (<= SMCMI_ENS_MAX_PARTS: a workgroup keeps two particle-length FP64 arrays in LDS, the stage's energies and the weights a
    selection accumulates - 128 KiB of a CU's 160 KiB at 8 192 particles), max_stages and store_history; they may differ in their seed,
    their model (priors, bounds, fixed flags) and their device likelihood family with its parameters and data.
+   PROGRAMS: instead of device families, every member may carry at SMCMI_WHICH_NEW the same program compiled for ensembles
+   (smcmi_program_compile_ensemble for the members' n_para: one code object, registered on each member with that member's own data and
+   par, which may differ in rows, cols and n_par).  The call then is one launch of that program's own copy of the kernel, with the dynamic
+   LDS of the library's own up to the largest cloud, and everything said here holds for it.
    After the call handle k is in the state smcmi_run(hs[k], rc, &res[k]) would have left it in - the cloud in the current buffer, the
    loop scalars on the device and in the host copy, the per-stage records, the w / W history (store_history), the last stage's moments -
    and every later call works as after a solo run.  The numbers are those of the solo run up to summation order (one workgroup's trees,
    the adaptive root certified to phi_rtol as smcmi_run_config defines it; no stage is predicted); a member's results do not depend on
    its position or its company, and two identical calls give the same bits.  res[k].seconds is the wall time of the whole call.
    Returns 0 when every member reached phi = 1.  A call that is refused as a whole returns the refusal's code, nothing ran and no handle
-   changed: n < 1, a NULL or repeated handle, members that differ in a shared shape -> SMCMI_ERR_ARG; a shard, a host or device
-   likelihood callback, an old-data likelihood or tempered_update_prior_weight != 0, stop_after_stage or continue_run, n_para > 10,
+   changed: n < 1, a NULL or repeated handle, members that differ in a shared shape, program members beside
+   family members, programs that are not one code object, a program compiled for another n_para -> SMCMI_ERR_ARG; a shard, a host or device
+   likelihood callback, a plain or fused program, a likelihood of any kind at SMCMI_WHICH_OLD or tempered_update_prior_weight != 0, stop_after_stage or continue_run, n_para > 10,
    n_parts > SMCMI_ENS_MAX_PARTS, and MIXTURE PROPOSALS (alpha < 1: refused, not served) -> SMCMI_ERR_UNSUPPORTED.  Otherwise the code
    of the lowest-indexed member that failed; status[k] (may be NULL) holds every member's own code - 0, SMCMI_ERR_NAN_ESS, _POSDEF,
    _CAPACITY, _BRACKET - and a failing member does not disturb the others. */

@@ -2827,6 +2827,10 @@ SMCMI_FP_CONTRACT
     if (debug & 2) { prior_new = lprior - 0.1 * zz2; like_new = like - 0.2; like_old_data = 0.0; }
     else if (inside()) {
         prior_new = prior();
+#ifdef SMCMI_PROGRAM_ENTRY
+        // a program is called on the rows the wrapper kernel's gate passes: in bounds and a log-prior above -Inf (the others keep -Inf, -Inf)
+        if (lv[0].family == SMCMI_LIK_PROGRAM && prior_new == SMCMI_NEG_INF) return;
+#endif
         like_new = loglik_s<D>(lv[0], XN);
         if (like_new == SMCMI_NEG_INF) prior_new = SMCMI_NEG_INF;
         like_old_data = (lv[1].family == SMCMI_LIK_NONE) ? 0.0 : loglik_s<D>(lv[1], XN);

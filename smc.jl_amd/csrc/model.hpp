@@ -78,7 +78,17 @@ struct LikView {
     long long rows, cols;
     const double *aux;
     long long aux_rows, aux_cols;
+#ifdef SMCMI_PROGRAM_ENTRY
+    long long n_par = 0;                     // family SMCMI_LIK_PROGRAM: the length of par, and this thread's tally of calls (a value, not a
+    mutable unsigned long long scored = 0ull;   // pointer: the view stays in registers; the MH step holds the view const)
+#endif
 };
+// A likelihood compiled at run time from HIP source, called from a register kernel (ensbody.hpp, compiled by the run-time compiler with
+// SMCMI_PROGRAM_ENTRY = the user's function): a family code no descriptor of the host carries, which loglik_s below serves.  Without the
+// define - every translation unit of the library - none of this exists.
+#ifdef SMCMI_PROGRAM_ENTRY
+constexpr int SMCMI_LIK_PROGRAM = 101;
+#endif
 
 template <class M, class Th>
 __device__ inline bool in_bounds(const M &m, Th th) {
@@ -875,6 +885,16 @@ __device__ inline double loglik(const L &l, int d, Th th) {
 template <int D, class L, class Th>
 __device__ inline double loglik_s(const L &l, Th th) {
     switch (l.family) {
+#ifdef SMCMI_PROGRAM_ENTRY
+    case SMCMI_LIK_PROGRAM: {    // the proposal as a private array, ld = 1 and d a literal: a source that loops k < d unrolls into registers
+        double xp[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) xp[k] = th(k);
+        l.scored += 1ull;
+        const double v = SMCMI_PROGRAM_ENTRY(xp, 1ll, D, l.data, l.rows, l.cols, l.par, l.n_par);
+        return v != v ? SMCMI_NEG_INF : v;      // NaN is taken as -Inf
+    }
+#endif
     case SMCMI_LIK_GAUSS_ISO: {
         const double sig = l.par[0];
         double acc = 0.0;

@@ -13,6 +13,7 @@
 #include "program.hpp"
 #include "progsrc.hpp"
 #include "fusedsrc.hpp"
+#include "enssrc.hpp"
 
 static_assert(program::EVAL_SLOTS == progsrc::EVAL_SLOTS && program::EVAL_STRIDE == progsrc::EVAL_STRIDE, "the wrapper text and the host disagree about the counter");
 
@@ -72,39 +73,43 @@ std::string rtc_text(int code) {
 
 namespace program {
 
-int compile(const char *source, const char *entry, const char *options, int32_t flags, smcmi_program **out, std::string *err) {
+int compile(const char *source, const char *entry, const char *options, int32_t flags, smcmi_program **out, std::string *err, int32_t ens_para) {
     if (out) *out = nullptr;
     if (!source || !out) { *err = "smcmi_program_compile: null argument"; return SMCMI_ERR_ARG; }
     if (flags & ~(int32_t)SMCMI_PROGRAM_FUSED) { *err = "smcmi_program_compile_ex: unknown flag bits"; return SMCMI_ERR_ARG; }
-    const bool fused = (flags & SMCMI_PROGRAM_FUSED) != 0;
+    // an ENSEMBLE compile (ens_para != 0; flags are 0 then) is a fused compile with another kernel: the same options, refusals and named headers
+    const bool ens = ens_para != 0;
+    if (ens && (ens_para < enssrc::PARA_MIN || ens_para > enssrc::PARA_MAX)) { *err = "smcmi_program_compile_ensemble: n_para outside 1..10"; return SMCMI_ERR_ARG; }
+    const bool fused = (flags & SMCMI_PROGRAM_FUSED) != 0, isolated = fused || ens;
     const char *ent = entry ? entry : progsrc::DEFAULT_ENTRY;
     if (!progsrc::valid_entry(ent)) { *err = "smcmi_program_compile: the entry is not a C identifier of at most 64 characters"; return SMCMI_ERR_ARG; }
     std::vector<std::string> extra;
     if (!progsrc::split_options(options, &extra, err)) return SMCMI_ERR_ARG;
-    if (fused && !fusedsrc::options_allowed(extra, err)) return SMCMI_ERR_ARG;
+    if (isolated && !fusedsrc::options_allowed(extra, err)) return SMCMI_ERR_ARG;
     if (!rtc_open(err)) return SMCMI_ERR_UNSUPPORTED;
     std::vector<std::string> opts = progsrc::base_options();
-    if (fused)
-        for (const std::string &o : fusedsrc::extra_options()) opts.push_back(o);
+    if (isolated)
+        for (const std::string &o : ens ? enssrc::extra_options() : fusedsrc::extra_options()) opts.push_back(o);
 #ifdef SMCMI_STRICT_FP
-    if (fused) opts.push_back("-DSMCMI_STRICT_FP");           // (the embedded kernels.hpp: the same contraction rule as this library's own)
+    if (isolated) opts.push_back("-DSMCMI_STRICT_FP");           // (the embedded kernels.hpp: the same contraction rule as this library's own)
 #endif
     opts.insert(opts.end(), extra.begin(), extra.end());
     std::vector<const char *> optv;
     for (const std::string &o : opts) optv.push_back(o.c_str());
-    const progsrc::Assembled text = fused ? fusedsrc::assemble(source, ent) : progsrc::assemble(source, ent);
-    // a fused program reaches the project's device headers and the stand-ins of the system headers as named headers, and nothing else
+    const progsrc::Assembled text = ens ? enssrc::assemble(source, ent, ens_para) : fused ? fusedsrc::assemble(source, ent) : progsrc::assemble(source, ent);
+    // a fused or ensemble program reaches the project's device headers and the stand-ins of the system headers as named headers, and nothing else
     std::vector<const char *> hdr_text, hdr_name;
-    if (fused)
-        for (const fusedsrc::Header &h : fusedsrc::header_table()) { hdr_name.push_back(h.name); hdr_text.push_back(h.text); }
+    if (isolated)
+        for (const fusedsrc::Header &h : ens ? enssrc::header_table() : fusedsrc::header_table()) { hdr_name.push_back(h.name); hdr_text.push_back(h.text); }
 
     rtc_prog prog = nullptr;
-    int rc = g_rtc.CreateProgram(&prog, text.text.c_str(), progsrc::USER_FILE, (int)hdr_name.size(), fused ? hdr_text.data() : nullptr,
-                                 fused ? hdr_name.data() : nullptr);
+    int rc = g_rtc.CreateProgram(&prog, text.text.c_str(), progsrc::USER_FILE, (int)hdr_name.size(), isolated ? hdr_text.data() : nullptr,
+                                 isolated ? hdr_name.data() : nullptr);
     if (rc != 0 || !prog) { *err = "hiprtcCreateProgram: " + rtc_text(rc); return SMCMI_ERR_HIP; }
     smcmi_program *p = new smcmi_program();
     p->entry = ent;
     p->fused = fused;
+    p->ens_para = ens_para;
     rc = g_rtc.CompileProgram(prog, (int)optv.size(), optv.data());
     size_t len = 0;
     if (g_rtc.GetProgramLogSize(prog, &len) == 0 && len > 1) {
@@ -119,6 +124,9 @@ int compile(const char *source, const char *entry, const char *options, int32_t 
             rc = g_rtc.GetCode(prog, p->code.data());
         }
         p->ok = rc == 0 && size > 0;
+        // the code object's identity: FNV-1a over its bytes (smcmi_run_ensemble: do two members carry the same program?)
+        p->id = 14695981039346656037ull;
+        for (const char c : p->code) p->id = (p->id ^ (unsigned char)c) * 1099511628211ull;
         if (!p->ok && p->log.empty()) p->log = "the run-time compiler returned no code object: " + rtc_text(rc);
     } else if (p->log.empty()) p->log = rtc_text(rc);
     g_rtc.DestroyProgram(&prog);
@@ -145,6 +153,15 @@ int load(const smcmi_program *p, Loaded *out, std::string *err) {
         if (e == hipSuccess && bytes != sizeof(out->abi)) e = hipErrorInvalidImage;
         if (e == hipSuccess) e = hipMemcpyDtoH(out->abi, words, sizeof(out->abi));
     }
+    hipFunction_t ensf = nullptr;
+    if (e == hipSuccess && p->ens_para != 0) {
+        e = hipModuleGetFunction(&ensf, mod, enssrc::ENSEMBLE_NAME);
+        hipDeviceptr_t words = nullptr;
+        size_t bytes = 0;
+        if (e == hipSuccess) e = hipModuleGetGlobal(&words, &bytes, mod, enssrc::ABI_NAME);
+        if (e == hipSuccess && bytes != sizeof(out->ens_abi)) e = hipErrorInvalidImage;
+        if (e == hipSuccess) e = hipMemcpyDtoH(out->ens_abi, words, sizeof(out->ens_abi));
+    }
     if (e != hipSuccess) {
         *err = std::string("loading the compiled likelihood: ") + hipGetErrorString(e);
         if (mod) (void)hipModuleUnload(mod);
@@ -154,6 +171,9 @@ int load(const smcmi_program *p, Loaded *out, std::string *err) {
     out->module = (void *)mod;
     out->kernel = (void *)fn;
     out->mutate = (void *)mut;
+    out->ensemble = (void *)ensf;
+    out->ens_para = ensf ? p->ens_para : 0;
+    out->id = p->id;
     return SMCMI_OK;
 }
 void unload(Loaded *l) {
@@ -161,6 +181,9 @@ void unload(Loaded *l) {
     l->module = nullptr;
     l->kernel = nullptr;
     l->mutate = nullptr;
+    l->ensemble = nullptr;
+    l->ens_para = 0;
+    l->id = 0;
 }
 
 unsigned grid_for(long long n) {
@@ -176,6 +199,11 @@ int launch_mutate(const Loaded &l, unsigned grid, unsigned block, size_t lds, vo
     // (more than 64 KiB of dynamic LDS: the runtime has no call that raises the maximum of a MODULE's function - hipFuncSetAttribute takes a
     // host function - and does not gate a module launch on it; the launch itself reports a request the device cannot serve)
     return (int)hipModuleLaunchKernel((hipFunction_t)l.mutate, grid, 1, 1, block, 1, 1, (unsigned)lds, (hipStream_t)stream, args, nullptr);
+}
+
+int launch_ensemble(const Loaded &l, unsigned grid, unsigned block, size_t lds, void **args, void *stream) {
+    // (dynamic LDS above 64 KiB: as launch_mutate)
+    return (int)hipModuleLaunchKernel((hipFunction_t)l.ensemble, grid, 1, 1, block, 1, 1, (unsigned)lds, (hipStream_t)stream, args, nullptr);
 }
 
 }      // namespace program

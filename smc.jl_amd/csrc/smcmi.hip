@@ -9,6 +9,7 @@
 #include "handle.hpp"
 #include "switches.hpp"
 #include "route.hpp"
+#include "ensbody.hpp"        // (EnsMember / EnsArgs: smcmi_set_likelihood_program compares an ensemble program's layout words with them)
 
 static constexpr size_t LS4_LDS = lds::mutate(lds::LS4_D, 16, 4, true).bytes;      // the four-lane k_mutate<0, 4>'s dynamic LDS
 
@@ -542,6 +543,18 @@ extern "C" int smcmi_program_compile_ex(const char *source, const char *entry, c
     const int rc = program::compile(source, entry, options, flags, out, &err);
     return rc ? set_err(rc, err) : 0;
 }
+extern "C" int smcmi_program_compile_ensemble(const char *source, const char *entry, const char *options, int32_t n_para, smcmi_program **out) {
+    if (out) *out = nullptr;
+    if (n_para < 1 || n_para > ENS_MAX_D) return set_err(SMCMI_ERR_ARG, "smcmi_program_compile_ensemble: n_para outside 1..10");
+    std::string err;
+    const int rc = program::compile(source, entry, options, 0, out, &err, n_para);
+    return rc ? set_err(rc, err) : 0;
+}
+extern "C" int smcmi_program_ensemble_para(const smcmi_program *p, int32_t *out) {
+    if (!p || !out) return set_err(SMCMI_ERR_ARG, "smcmi_program_ensemble_para: null argument");
+    *out = p->ens_para;
+    return 0;
+}
 extern "C" int smcmi_program_is_fused(const smcmi_program *p, int32_t *out) {
     if (!p || !out) return set_err(SMCMI_ERR_ARG, "smcmi_program_is_fused: null argument");
     *out = p->fused ? 1 : 0;
@@ -575,6 +588,12 @@ extern "C" int smcmi_set_likelihood_program(smcmi_handle *h, int32_t which, cons
         if (mod.mutate && memcmp(abi, mod.abi, sizeof(abi)) != 0) {
             program::unload(&mod);
             return set_err(SMCMI_ERR_STATE, "the fused program was compiled against other struct layouts than this library's");
+        }
+        // ... and an ensemble kernel reads the member table, its arguments, DevState and ModelDev
+        const unsigned ens_abi[4] = {(unsigned)sizeof(EnsMember), (unsigned)sizeof(EnsArgs), (unsigned)sizeof(DevState), (unsigned)sizeof(ModelDev)};
+        if (mod.ensemble && memcmp(ens_abi, mod.ens_abi, sizeof(ens_abi)) != 0) {
+            program::unload(&mod);
+            return set_err(SMCMI_ERR_STATE, "the ensemble program was compiled against other struct layouts than this library's");
         }
         bool ok = h->d_prog_evals || dmalloc(h->mem, &h->d_prog_evals, (size_t)program::EVAL_WORDS) == 0;
         if (ok && rows * cols > 0) ok = dmalloc(h->mem, &d_data, (size_t)(rows * cols)) == 0 && hipMemcpy(d_data, data, sizeof(double) * rows * cols, hipMemcpyHostToDevice) == hipSuccess;

@@ -105,6 +105,8 @@ SYMBOLS = [
     ("smcmi_program_compile", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     ("smcmi_program_compile_ex", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
     ("smcmi_program_is_fused", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    ("smcmi_program_compile_ensemble", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    ("smcmi_program_ensemble_para", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     ("smcmi_program_log", C.c_char_p, [C.c_void_p]),
     ("smcmi_program_code", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), lp]),
     ("smcmi_program_destroy", C.c_int, [C.c_void_p]),

@@ -209,19 +209,29 @@ class HIPLikelihood:
     long long cols, const double *par, long long n_par)` with theta[j * ld] parameter j of the proposal.  smc(HIPLikelihood(source),
     parameters, data, ...) hands `data` (2-d, column-major on the device) and `par` to the function and routes it through
     Engine.set_likelihood_program: one launch per MH step x block, nothing read by the host.  fused=True compiles the function into the
-    generic mutation kernel as well (a compile of about half a second): a run that is not tempered then mutates a stage in one launch, same bits."""
+    generic mutation kernel as well (a compile of about half a second): a run that is not tempered then mutates a stage in one launch, same bits.
+    ensemble=True marks the likelihood for smc_ensemble(): the function is compiled into the ensemble kernel, for the number of parameters
+    of the call, and all seeds run in one launch."""
 
-    def __init__(self, source, par=None, entry="loglik", options=None, fused=False):
+    def __init__(self, source, par=None, entry="loglik", options=None, fused=False, ensemble=False):
         if not isinstance(source, (str, bytes)):
             raise TypeError("HIPLikelihood takes the likelihood's HIP source as text")
         self.source, self.par, self.entry, self.options, self.fused = source, par, entry, options, bool(fused)
+        self.ensemble = bool(ensemble)
         self._program = None
+        self._ensemble_programs = {}
 
     def program(self):
         """the compiled program (compiled on first use; a compiler error raises CompileError with the log)"""
         if self._program is None:
             self._program = Engine.compile_program(self.source, entry=self.entry, options=self.options, fused=self.fused)
         return self._program
+
+    def ensemble_program(self, n_para):
+        """the program compiled for ensembles of n_para parameters (compiled on first use, once per n_para)"""
+        if n_para not in self._ensemble_programs:
+            self._ensemble_programs[n_para] = Engine.compile_program(self.source, entry=self.entry, options=self.options, ensemble_para=n_para)
+        return self._ensemble_programs[n_para]
 
 
 def _lik_kind(lik):
@@ -542,14 +552,18 @@ def smc_ensemble(loglikelihood, parameters, data, seeds, *, n_parts=5000, n_bloc
                  tempering_target=0.97, device=0, max_stages=None, regime_switching=False, verbose="none"):
     """The same estimation over many seeds in ONE launch, one workgroup per seed (Engine-level: run_ensemble; C ABI:
     smcmi_run_ensemble) - what a loop of smc(..., seed=s) calls computes, e.g. for the standard deviation of the log-MDD over seeds.
-    Device likelihood families only, n_para <= 10, n_parts <= 8192, alpha = 1, no tempered update.  Returns one (cloud, w, W) per
+    Device likelihood families, or a HIPLikelihood(source, ensemble=True): compiled once for the call's number of parameters, registered on
+    every seed's engine with `data` and its par, the initial clouds drawn through the program's wrapper kernel, then one launch.
+    n_para <= 10, n_parts <= 8192, alpha = 1, no tempered update.  Returns one (cloud, w, W) per
     seed, in the order of `seeds`, each as smc() returns it; cloud.status is the member's own code (0: it reached phi = 1)."""
     from . import _lib
     from .engine import run_ensemble
 
-    if not isinstance(loglikelihood, DeviceLikelihood):
-        raise NotImplementedError("smc_ensemble() takes a device likelihood (GaussIso, LinReg, LinModel3, CapmLiteral); a Python callable, "
-                                  "a TorchLikelihood or a HIPLikelihood runs through smc(), one seed per call")
+    hip = isinstance(loglikelihood, HIPLikelihood) and loglikelihood.ensemble
+    if not isinstance(loglikelihood, DeviceLikelihood) and not hip:
+        raise NotImplementedError("smc_ensemble() takes a device likelihood (GaussIso, LinReg, LinModel3, CapmLiteral) or a "
+                                  "HIPLikelihood(source, ensemble=True); a Python callable, a TorchLikelihood or a HIPLikelihood without "
+                                  "ensemble=True runs through smc(), one seed per call")
     if verbose not in VERBOSITY:
         raise ValueError("verbose must be one of :none, :low, :high")
     if resampling_method not in ("systematic", "multinomial", "polyalgo"):
@@ -565,7 +579,8 @@ def smc_ensemble(loglikelihood, parameters, data, seeds, *, n_parts=5000, n_bloc
         raise NotImplementedError("smc_ensemble() serves n_para <= %d, n_parts <= %d and alpha = 1; smc() serves the rest"
                                   % (_lib.ENS_MAX_PARA, _lib.ENS_MAX_PARTS))
     data = np.asarray(data, dtype=np.float64)
-    spec = _spec_from(parameters, loglikelihood.spec(data), None)
+    spec = _spec_from(parameters, _lik_spec(loglikelihood, data) if hip else loglikelihood.spec(data), None)
+    prog = loglikelihood.ensemble_program(d) if hip else None
     if max_stages is None:
         max_stages = n_phi if use_fixed_schedule else 4 * n_phi + 64
     engines = []
@@ -573,7 +588,12 @@ def smc_ensemble(loglikelihood, parameters, data, seeds, *, n_parts=5000, n_bloc
         for s in seeds:
             e = Engine(n_parts, d, seed=s, device=device, max_stages=max_stages, store_history=True)
             engines.append(e)
-            e.set_model(spec)
+            if hip:
+                e.set_parameters(spec["priors"], spec["bounds"], spec["fixed"])
+                e.set_likelihood_program(prog, data=data, par=loglikelihood.par, which=0)
+                e.set_likelihood("none", which=1)
+            else:
+                e.set_model(spec)
             e.init_from_prior()
         rs = run_ensemble(engines, n_blocks=n_blocks, n_mh_steps=n_mh_steps, lam=lam, n_phi=n_phi, resampling_method=resampling_method,
                           threshold_ratio=threshold_ratio, c=c, alpha=alpha, target=target, use_fixed_schedule=use_fixed_schedule,

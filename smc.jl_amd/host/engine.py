@@ -35,13 +35,19 @@ class CompileError(_lib.SMCMIError):
 class Program:
     """A likelihood compiled from HIP source (include/smcmi.h smcmi_program_*): host memory only, tied to no engine and no device.
     fused=True (SMCMI_PROGRAM_FUSED): the function is compiled into the generic mutation kernel as well - one launch per stage where the
-    run allows it, a compile of about half a second."""
+    run allows it, a compile of about half a second.
+    ensemble_para=d (smcmi_program_compile_ensemble): the function is compiled into the ensemble kernel for n_para = d (1..10) instead -
+    registered on every member, run_ensemble runs all members' whole runs in one launch."""
 
-    def __init__(self, source, entry="loglik", options=None, fused=False):
+    def __init__(self, source, entry="loglik", options=None, fused=False, ensemble_para=None):
         L = _lib.lib()
         self._L, self._p = L, C.c_void_p()
         enc = lambda s: None if s is None else s.encode() if isinstance(s, str) else bytes(s)
-        if fused:
+        if ensemble_para is not None:
+            if fused:
+                raise ValueError("a program is compiled either fused or for ensembles")
+            rc = L.smcmi_program_compile_ensemble(enc(source), enc(entry), enc(options), int(ensemble_para), C.byref(self._p))
+        elif fused:
             rc = L.smcmi_program_compile_ex(enc(source), enc(entry), enc(options), _lib.PROGRAM_FUSED, C.byref(self._p))
         else:
             rc = L.smcmi_program_compile(enc(source), enc(entry), enc(options), C.byref(self._p))
@@ -62,6 +68,13 @@ class Program:
         v = C.c_int32()
         check(self._L.smcmi_program_is_fused(self._p, C.byref(v)))
         return bool(v.value)
+
+    @property
+    def ensemble_para(self):
+        """the n_para of a program compiled for ensembles, 0 for any other"""
+        v = C.c_int32()
+        check(self._L.smcmi_program_ensemble_para(self._p, C.byref(v)))
+        return int(v.value)
 
     @property
     def code(self):
@@ -192,14 +205,16 @@ class Engine:
         check(self._L.smcmi_set_likelihood_device(self._h, which, C.byref(st)))
 
     @staticmethod
-    def compile_program(source, entry="loglik", options=None, fused=False):
+    def compile_program(source, entry="loglik", options=None, fused=False, ensemble_para=None):
         """Compile a likelihood given as HIP source (smcmi_program_compile; needs no GPU and no engine): the source defines
         `__device__ double loglik(const double *theta, long long ld, int d, const double *data, long long rows, long long cols,
         const double *par, long long n_par)` with theta[j * ld] parameter j of the proposal.  Returns a Program; a compiler error
         raises CompileError, whose .log has the compiler's messages with the line numbers of `source` (likelihood.hip:<line>).
         fused=True (smcmi_program_compile_ex, SMCMI_PROGRAM_FUSED): the function is also compiled into the generic mutation kernel - a
-        run that is not tempered then mutates a stage in one launch, with the bits of the split path."""
-        return Program(source, entry=entry, options=options, fused=fused)
+        run that is not tempered then mutates a stage in one launch, with the bits of the split path.
+        ensemble_para=d (smcmi_program_compile_ensemble): the function is compiled into the ensemble kernel for n_para = d instead;
+        registered on every member with the member's own data and par, run_ensemble runs the members' whole runs in one launch."""
+        return Program(source, entry=entry, options=options, fused=fused, ensemble_para=ensemble_para)
 
     def set_likelihood_program(self, program_or_source, data=None, par=None, which=0, fused=False):
         """Register a compiled likelihood (smcmi_set_likelihood_program): a Program, or source text that is compiled first (fused: as

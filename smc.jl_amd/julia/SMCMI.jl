@@ -157,15 +157,18 @@ lik_aux(::Any) = zeros(0, 0)
 # smc(HIPLikelihood(source; par = [...]), parameters, data; kwargs...) runs it; old_loglikelihood may be another HIPLikelihood.
 # fused = true (SMCMI_PROGRAM_FUSED): the function is compiled into the generic mutation kernel as well - a compile of about half a second, and a run
 # that is not tempered mutates a stage in one launch, with the bits of the split path.
+# ensemble_para = d > 0 (smcmi_program_compile_ensemble): the function is compiled into the ensemble kernel for n_para = d instead; registered
+# on every member of run_ensemble!, all members' whole runs are one launch.
 struct HIPLikelihood
     source::String
     par::Vector{Float64}
     entry::String
     options::Union{Nothing, String}
     fused::Bool
+    ensemble_para::Int32
 end
-HIPLikelihood(source::AbstractString; par = Float64[], entry = "loglik", options = nothing, fused = false) =
-    HIPLikelihood(String(source), Float64[x for x in par], String(entry), options, Bool(fused))
+HIPLikelihood(source::AbstractString; par = Float64[], entry = "loglik", options = nothing, fused = false, ensemble_para = 0) =
+    HIPLikelihood(String(source), Float64[x for x in par], String(entry), options, Bool(fused), Int32(ensemble_para))
 const Program = Ptr{Cvoid}                                   # smcmi_program *
 struct CompileError <: Exception
     code::Int
@@ -175,13 +178,21 @@ Base.showerror(io::IO, e::CompileError) = print(io, "SMCMI: the likelihood sourc
 function compile_program(lik::HIPLikelihood)
     p = Ref{Program}(C_NULL)
     opts = lik.options === nothing ? Cstring(C_NULL) : lik.options
-    rc = ccall((:smcmi_program_compile_ex, LIB), Cint, (Cstring, Cstring, Cstring, Int32, Ref{Program}), lik.source, lik.entry, opts, Int32(lik.fused ? 1 : 0), p)
+    rc = lik.ensemble_para > 0 ?
+        ccall((:smcmi_program_compile_ensemble, LIB), Cint, (Cstring, Cstring, Cstring, Int32, Ref{Program}), lik.source, lik.entry, opts, lik.ensemble_para, p) :
+        ccall((:smcmi_program_compile_ex, LIB), Cint, (Cstring, Cstring, Cstring, Int32, Ref{Program}), lik.source, lik.entry, opts, Int32(lik.fused ? 1 : 0), p)
     if rc != 0
         log = p[] == C_NULL ? "" : unsafe_string(ccall((:smcmi_program_log, LIB), Cstring, (Ptr{Cvoid},), p[]))
         p[] == C_NULL || ccall((:smcmi_program_destroy, LIB), Cint, (Ptr{Cvoid},), p[])
         rc == -11 ? throw(CompileError(rc, log)) : check(rc)
     end
     p[]
+end
+# the n_para a program was compiled for ensembles with, 0 for any other program
+function program_ensemble_para(p::Program)
+    v = Ref{Int32}(0)
+    check(ccall((:smcmi_program_ensemble_para, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), p, v))
+    Int(v[])
 end
 function set_program!(h::Handle, lik::HIPLikelihood, data::Matrix{Float64}, which::Integer)
     p = compile_program(lik)
