@@ -390,6 +390,13 @@ int smcmi_mailbox_import(smcmi_handle *h, int32_t rank, int32_t world, const uin
 int smcmi_mailbox_selftest(smcmi_handle *h, int32_t rank, int32_t world, int32_t rounds, int32_t *errors_out);
 int smcmi_mailbox_active(smcmi_handle *h, int32_t *active_out);   /* 1: the last sharded run handed its per-stage sums over through the mailbox */
 int smcmi_run_group(smcmi_handle **hs, int32_t n, const smcmi_run_config *rc, smcmi_result *res);
+/* Which translation unit's segment kernel the handle's last segment launch ran (tests; the units compute the same bits):
+   SMCMI_SEG_UNIT_NONE no segment launch yet, _RUN the default-run unit (one handle, alpha = 1, adaptive or exact-shift schedule, one random
+   block, more than 8 192 particles, no development stamps), _GENERAL any other unit. */
+#define SMCMI_SEG_UNIT_NONE 0
+#define SMCMI_SEG_UNIT_RUN 1
+#define SMCMI_SEG_UNIT_GENERAL 2
+int smcmi_segment_unit(smcmi_handle *h, int32_t *unit_out);
 /* ---- an ensemble of small runs in ONE launch (csrc/runens.hpp, csrc/ensbody.hpp) -------------------------------------------------
    The reference's workloads are small (n_parts defaults to 5 000, its examples use 1 000) and are run many times over: seeds, data
    vintages, model variants.  smcmi_run_ensemble runs n such runs at once, ONE WORKGROUP PER RUN: member k runs the whole loop of

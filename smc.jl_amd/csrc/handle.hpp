@@ -56,7 +56,9 @@ struct Eng2 {
     unsigned long long *h_res = nullptr, *d_res = nullptr;
     int seg_ch = 1;                  // 512-particle chunks per segment worker (2: one handle of 126 977 .. 253 952 particles, α = 1, a cheap likelihood)
     int e3_state = 0;                // 0 untested, 1 usable (residency self-test passed), -1 off for this handle
-    int seg_attr_set = 0;         /* bits 0 / 1: α = 1 / mixture variant, bits 2 / 3: their riding instantiations, bits 4 / 5: two chunks per worker */       // k3_segment's dynamic-LDS opt-in done on this handle's device
+    int seg_attr_set = 0;         /* bits 0 / 1: α = 1 / mixture variant, bits 2 / 3: their riding instantiations, bits 4 / 5: two chunks per worker, bits 6-9: several handles, bit 10: the default-run unit */       // k3_segment's dynamic-LDS opt-in done on this handle's device
+    int seg_unit = 0;                // SMCMI_SEG_UNIT_*: the unit the last segment launch took (launch2.hpp launch_k3_segment; smcmi_segment_unit)
+    bool seg_general = false;        // SMCMI_K3_GENERAL=1 (development): the general unit wherever the default-run unit would run
     bool wide_attr_set = false;      // k2w_mutate's dynamic-LDS opt-in done on this handle's device
     bool rng_ahead = false;          // K1 carries blocks that draw the mutation's random numbers into the handle's zbuf
     int n_steps = 1, n_blocks = 1;

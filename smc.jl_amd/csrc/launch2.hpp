@@ -128,8 +128,48 @@ int launch_k3_seg(smcmi_handle *h, const Mut2Args &ma, const Seg3Args &sa, int n
     }
     return 0;
 }
+// THE DEFAULT-RUN UNIT of k3_segment<D, true, false> (stage3.hpp SMCMI_K3_RUN: no stamps, gatherer geometry, one random block),
+// translation units of its own (inst3_d<D>, next to the general unit's inst3g_d<D>): defined there alone, a symbol to everyone else
+template <int D>
+int launch_k3_seg_run(smcmi_handle *h, const Mut2Args &ma, const Seg3Args &sa, int nb);
+#ifdef SMCMI_K3_RUN
+template <int D>
+int launch_k3_seg_run(smcmi_handle *h, const Mut2Args &ma, const Seg3Args &sa, int nb) {
+    Eng2 *e = h->e2;
+    constexpr lds::Seg3Layout O3 = k3_layout(D, true, 1);
+    const size_t lds = std::max(O3.bytes, e->g.nb2 > GRP ? O3.gather_bytes : (size_t)0);      // (as launch_k3_seg)
+    const unsigned grid = (unsigned)(e->g.Vl * e->g.nb2 + e->g.Vl);                            // workers + one gatherer per virtual shard, always
+    constexpr int attr_bit = 1 << 10;
+    if (!(e->seg_attr_set & attr_bit)) {
+        if (set_max_lds(defrun::k3_segment<D, true, false>, k3_max_lds_bytes(D, true, 1))) return SMCMI_ERR_HIP;
+        e->seg_attr_set |= attr_bit;
+    }
+    Mut2Args mk = ma;
+    if constexpr ((k3_fast_bits(true, false, 1, false) & A1F_PRIOR) != 0) mk.has_other = h->h_model.prior_shape;
+    defrun::k3_segment<D, true, false><<<grid, T3, lds, h->stream>>>(h->cl, h->d_st, e->d_ctl, h->d_model, e->g, mk, sa, nb, h->h_model.n_free);
+    return 0;
+}
+#endif
+// which unit a launch of the α = 1, two-hand-over, one-handle, one-chunk kernel takes: the default-run unit exactly when the launch is what that
+// unit was compiled for (stage3.hpp K3U_*); anything else - and everything under SMCMI_K3_GENERAL=1 (Eng2::seg_general) - the general unit.
+// Both leave memory alike: the batches of one run may differ in it.  (SMCMI_K3_KEEP & 1, development builds: the unit has its stamps)
+inline bool k3_takes_run_unit(const Eng2 *e, const Seg3Args &sa, int nb) {
+#if defined(SMCMI_K3_KEEP) && ((SMCMI_K3_KEEP) & 1)
+    const bool stamps_ok = true;
+#else
+    const bool stamps_ok = sa.prof == nullptr && sa.gprof == nullptr;
+#endif
+    return !e->seg_general && nb == 1 && e->g.nb2 > 2 && stamps_ok;
+}
 template <int D>
 inline int launch_k3_segment(smcmi_handle *h, const Mut2Args &ma, const Seg3Args &sa, int nb, bool alpha1, bool ride) {
+    h->e2->seg_unit = SMCMI_SEG_UNIT_GENERAL;
+    if constexpr (D <= 10) {
+        if (h->e2->seg_ch != 2 && sa.peers == nullptr && alpha1 && !ride && k3_takes_run_unit(h->e2, sa, nb)) {
+            h->e2->seg_unit = SMCMI_SEG_UNIT_RUN;
+            return launch_k3_seg_run<D>(h, ma, sa, nb);
+        }
+    }
     if (h->e2->seg_ch == 2)               // (seg3_ready grants two chunks to α = 1 runs only)
         return ride ? launch_k3_seg<D, true, true, 2>(h, ma, sa, nb) : launch_k3_seg<D, true, false, 2>(h, ma, sa, nb);
     if (sa.peers != nullptr) {            // several handles
@@ -172,7 +212,11 @@ SMCMI_LAUNCH_B_D(SMCMI_LAUNCH3_INSTANCES, extern)
 SMCMI_LAUNCH_B_D(SMCMI_LAUNCH2B_INSTANCES, extern)
 #elif defined(SMCMI_INST3_D)
 SMCMI_LAUNCH_ALL_D(SMCMI_LAUNCH2_INSTANCES, extern)
+#ifdef SMCMI_K3_RUN
+template int launch_k3_seg_run<SMCMI_INST3_D>(smcmi_handle *, const Mut2Args &, const Seg3Args &, int);
+#else
 SMCMI_LAUNCH3_ONE(SMCMI_INST3_D, (SMCMI_INST3_A != 0), (SMCMI_INST3_R != 0), SMCMI_INST3_C, (SMCMI_INST3_S != 0))
+#endif
 SMCMI_LAUNCH_B_D(SMCMI_LAUNCH2B_INSTANCES, extern)
 #elif defined(SMCMI_INST2B_D)
 SMCMI_LAUNCH_ALL_D(SMCMI_LAUNCH2_INSTANCES, extern)

@@ -622,6 +622,7 @@ static int run2_impl(ShardGroup &g, const smcmi_run_config *rc, smcmi_result *re
         sa.prof = (h == h0 && e->d_prof && n_first <= e->prof_stage && e->prof_stage <= n_last) ? e->d_prof + PROF2_SEG0 : nullptr;
         sa.prof_stage = e->prof_stage;
         sa.gprof = sa.prof ? e->d_prof : nullptr;            // (the wall-clock stamps of every block: absolute PROF2_* offsets)
+        e->seg_general = sw().k3_general != 0;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (profile && sa.done_out) { HIP_TRY(evs3.event(&e0)); HIP_TRY(evs3.event(&e1)); hipEventRecord(e0, h->stream); }       // (pair k belongs to launch k)
         // (the stage counters of all launches of a run are cleared once, in front of its first segment: a fill per launch was 5 µs each)

@@ -1493,6 +1493,11 @@ extern "C" int smcmi_mailbox_active(smcmi_handle *h, int32_t *active_out) {
     *active_out = h->mbox_used ? 1 : 0;
     return 0;
 }
+extern "C" int smcmi_segment_unit(smcmi_handle *h, int32_t *unit_out) {
+    if (!h || !unit_out) return set_err(SMCMI_ERR_ARG, "null argument");
+    *unit_out = h->e2 ? h->e2->seg_unit : SMCMI_SEG_UNIT_NONE;
+    return 0;
+}
 
 // (down here: the structs a handle owns - Eng2, the callback buffers - are complete types by now)
 extern "C" int smcmi_destroy(smcmi_handle *h) {

@@ -820,6 +820,43 @@ __device__ inline void k3_leave_note(const Seg3Args &sa, const Ctl2 *ctl) {
     if (threadIdx.x == 0) __hip_atomic_store(sa.note, sa.note_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// THE DEFAULT-RUN UNIT (defrun::k3_segment<D, true, false>; inst3.hip with -DSMCMI_INST3_U=1 defines SMCMI_K3_RUN; launch2.hpp launch_k3_seg_run):
+// the α = 1, two-hand-over, one-handle, one-chunk kernel as the default run of one cloud of more than 8 192 particles takes it, compiled from
+// this same kernel body with three things fixed that such a launch never varies - text it never reaches, but whose operands the general unit
+// holds in registers across the stage loop:
+//   K3U_STAMPS  no development stamps (K3_STAMP, K3_WALL, K3S, the prof pointers handed on: SMCMI_PROF2 alone sets them)
+//   K3U_ROWS    gatherer geometry only (g.nb2 > 2: neither rows_direct nor rows_two)
+//   K3U_NB      one random block (the kernel argument nb is ignored)
+// Each is 1 where the text stays general: in every other unit all three, in this one the bits of SMCMI_K3_KEEP (a compile flag of development
+// builds, Makefile VARIANT_FLAGS: 1 keeps the stamps - the unit's phase table, tools/phase_isa.py; 2 / 4 the other two - what each is
+// worth, profiles/r20_segment_units.json).  The differences are text (cf. SMCMI_K3_CH2 below): every other unit expands to what it was.
+// (Mut2Args::debug fixed at 0 as a fourth was measured and left out: the unit was no faster with it - DESIGN §9.1.)
+#ifdef SMCMI_K3_RUN
+#ifndef SMCMI_K3_KEEP
+#define SMCMI_K3_KEEP 0
+#endif
+#define K3U_STAMPS (((SMCMI_K3_KEEP) & 1) != 0)
+#define K3U_ROWS (((SMCMI_K3_KEEP) & 2) != 0)
+#define K3U_NB (((SMCMI_K3_KEEP) & 4) != 0)
+#else
+#define K3U_STAMPS 1
+#define K3U_ROWS 1
+#define K3U_NB 1
+#endif
+#if K3U_STAMPS
+#define K3_PROF(p) (p)
+#else
+#define K3_PROF(p) nullptr
+#endif
+#if K3U_ROWS
+#define K3_SEL_ROWS_DIRECT rows_direct
+#define K3_SEL_ROWS_TWO rows_two
+#else
+#define K3_SEL_ROWS_DIRECT false
+#define K3_SEL_ROWS_TWO false
+#endif
+
+#if K3U_STAMPS
 #define K3_STAMP(prof, slot)                                                                                                   \
     do {                                                                                                                      \
         if ((prof) != nullptr && threadIdx.x == 0 && blockIdx.x == 0 && n == sa.prof_stage) {                                                        \
@@ -828,6 +865,9 @@ __device__ inline void k3_leave_note(const Seg3Args &sa, const Ctl2 *ctl) {
             (prof)[(slot)] = (long long)tt_;                                                                                   \
         }                                                                                                                     \
     } while (0)
+#else
+#define K3_STAMP(prof, slot) (void)0
+#endif
 
 // a lane's flag, kept in a vector register, as a predicate formed HERE (K3H_LIVE: the empty asm is opaque to the compiler, so the compare
 // cannot move in front of it - out of a loop, into a scalar register pair that lives across it)
@@ -851,10 +891,14 @@ __device__ __forceinline__ bool k3_lane_flag(int &f) {
 
 // (development, SMCMI_PROF2: the hand-overs of the profiled stage on the 100 MHz wall clock, which all dies share - worker b's slots at
 // PROF2_WORK + 4 b, gatherer v's at PROF2_GATH + 6 v (stage2.hpp: the buffer's layout); prof2.hpp prints the spread)
+#if K3U_STAMPS
 #define K3_WALL(prof, idx)                                                                                                    \
     do {                                                                                                                      \
         if ((prof) != nullptr && threadIdx.x == 0 && n == sa.prof_stage) (prof)[(idx)] = wall_clock64();                       \
     } while (0)
+#else
+#define K3_WALL(prof, idx) (void)0
+#endif
 
 // SELECTION inside the segment (src/smc_main.jl:435-446, src/resample.jl:23-72): what k2_scan + k2_gather do between two launches, by the
 // workers on the particles they hold - the same functions on the same 512-particle blocks, hence the same cum column, ancestors and moment
@@ -874,7 +918,11 @@ __device__ __attribute__((noinline)) int k3_select_inside(const Sel3Args *selp, 
                                                           const unsigned long long *g_cm, unsigned long long *to, int *s_to, double *s_tot, double *s_vt, double *s_sw,
                                                           double *red, double *sc, double *stx, double *sto, const double *shift, long long *pf, bool rows_direct, bool rows_two
                                                           K3_SEL_DB_PARAM) {
+#if K3U_STAMPS
 #define K3S(k) do { if (pf && threadIdx.x == 0) pf[k] = wall_clock64(); } while (0)
+#else
+#define K3S(k) (void)0
+#endif
     constexpr int NPm = Mut2Lds<D>::NP, MGM = pad2(NPm), DAm = D + 1, NPF = Mut2Lds<D>::NPF, MCM = pad2(NPF);
     const Sel3Args sl = *selp;
     const int tid = threadIdx.x;
@@ -945,8 +993,8 @@ __device__ __attribute__((noinline)) int k3_select_inside(const Sel3Args *selp, 
     __syncthreads();
     K3S(3);
     if (tid < 2) gran_store(sl.g_sel + ((long long)rowi * 2 + tid) * 2, 0.0, tag);
-    if (!(rows_two ? gather_totals<2>(sl.g_sel, V, 2, -1, tag, to, s_to, s_sw, s_vt)
-                   : gather_totals(sys ? sl.mine + sl.off_sel : (rows_direct ? sl.g_sel : sl.gt_sel), V, 2, -1, tag, to, s_to, s_sw, s_vt, sys))) return 1;
+    if (!(K3_SEL_ROWS_TWO ? gather_totals<2>(sl.g_sel, V, 2, -1, tag, to, s_to, s_sw, s_vt)
+                   : gather_totals(sys ? sl.mine + sl.off_sel : (K3_SEL_ROWS_DIRECT ? sl.g_sel : sl.gt_sel), V, 2, -1, tag, to, s_to, s_sw, s_vt, sys))) return 1;
     K3S(4);
     // (5) ancestors of my output slots
     double u_sys = 0.0, ub_;
@@ -1023,8 +1071,8 @@ __device__ __attribute__((noinline)) int k3_select_inside(const Sel3Args *selp, 
     // thread writes the slots it alone reads.  The particle in transit (stx, sto) lies behind the parking area (ldslayout.hpp seg3) or in device memory.
     k3_draw_park<D, MIXDRAW>(sc, seed, (unsigned long long)(gid0 + i), (unsigned)n, db);
 #endif
-    if (!(rows_two ? gather_totals<2>(sl.g_gm, V, MGM, -1, tag, to, s_to, s_tot + 2, s_vt)
-                   : gather_totals(sys ? sl.mine + sl.off_gm : (rows_direct ? sl.g_gm : sl.gt_gm), V, MGM, -1, tag, to, s_to, s_tot + 2, s_vt, sys))) return 1;
+    if (!(K3_SEL_ROWS_TWO ? gather_totals<2>(sl.g_gm, V, MGM, -1, tag, to, s_to, s_tot + 2, s_vt)
+                   : gather_totals(sys ? sl.mine + sl.off_gm : (K3_SEL_ROWS_DIRECT ? sl.g_gm : sl.gt_gm), V, MGM, -1, tag, to, s_to, s_tot + 2, s_vt, sys))) return 1;
     K3S(9);
     return 0;
 #undef K3S
@@ -1277,8 +1325,17 @@ __device__ inline bool k3_rides(const RunParams &rp, const Seg3Args &sa, const P
 constexpr int k3_fast_bits(bool alpha1, bool ride, int ch, bool sys) {
     return alpha1 ? ((SMCMI_A1FAST) | ((!ride && ch == 1 && !sys) ? ((SMCMI_A1TARGET) | (SMCMI_A1FUSE)) : 0)) : 0;
 }
+#ifdef SMCMI_K3_RUN
+// (the default-run unit: this translation unit's kernel is defrun::k3_segment; the general kernel is another unit's - declared for launch2.hpp)
+template <int D, bool ALPHA1, bool RIDE, int CH = 1, bool SYS = false>
+__global__ void k3_segment(CloudPtrs cl, DevState *st, Ctl2 *ctl, const ModelDev *md, Geo2 g, Mut2Args ma, Seg3Args sa, int nb, int nf);
+namespace defrun {
+#endif
 template <int D, bool ALPHA1, bool RIDE, int CH = 1, bool SYS = false>
 __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, DevState *st, Ctl2 *ctl, const ModelDev *md, Geo2 g, Mut2Args ma, Seg3Args sa, int nb, int nf) {
+#if !K3U_NB
+    nb = 1;
+#endif
     constexpr int NPF = Mut2Lds<D>::NPF, MCM = pad2(NPF);
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ RecA3 s_a;
@@ -1311,7 +1368,11 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
 #if (K3HO) & K3H_FETCH
     __shared__ K3Ho s_ho;                                       // (k3_totals: what its calls have in common)
     if (tid == 64) {
+#if K3U_ROWS
         const bool direct = g.nb2 == 1;                         // (rows_direct below: the workers take each other's rows, no gatherer runs)
+#else
+        constexpr bool direct = false;
+#endif
         s_ho.tbl[0] = direct ? sa.g_cm : sa.gt_cm; s_ho.tbl[1] = direct ? sa.g_mut : sa.gt_mut;
         s_ho.to = sa.to; s_ho.tot = (K3_LDS double *)s_tot; s_ho.vt = (K3_LDS double *)s_vt; s_ho.s_to = (K3_LDS int *)&s_to; s_ho.nvs = g.V;
     }
@@ -1322,7 +1383,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
         const int vg_ = (int)blockIdx.x - W;
         s_gh.tbl[0] = sa.g_cm + (long long)vg_ * g.nb2 * MCM * 2; s_gh.tbl[1] = sa.g_mut + (long long)vg_ * g.nb2 * RMUT * 2;
         s_gh.dst[0] = sa.gt_cm + (long long)(g.v0 + vg_) * MCM * 2; s_gh.dst[1] = sa.gt_mut + (long long)(g.v0 + vg_) * RMUT * 2;
-        s_gh.to = sa.to; s_gh.pw = sa.gprof ? sa.gprof + PROF2_GPOLL + 4 * vg_ : nullptr; s_gh.ptag = sa.tag_base | (unsigned)sa.prof_stage;
+        s_gh.to = sa.to; s_gh.pw = K3_PROF(sa.gprof ? sa.gprof + PROF2_GPOLL + 4 * vg_ : nullptr); s_gh.ptag = sa.tag_base | (unsigned)sa.prof_stage;
         s_gh.stage = (K3_LDS double *)lds_at<double, O3[lds::S_gather]>(sm); s_gh.s_to = (K3_LDS int *)&s_to; s_gh.nr = g.nb2;
     }
 #endif
@@ -1593,8 +1654,12 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     // one handle whose virtual shards are ONE block each (clouds of up to 4 096 particles): a shard's total is its only row (the canonical
     // sum of one row adds zeros to it), so every worker takes the V rows themselves - one hop per hand-over instead of two; no gatherer is
     // launched for such a cloud (launch2.hpp launch_k3_seg)
+#if K3U_ROWS
     const bool rows_direct = g.nb2 == 1 && !sys;
     const bool rows_two = g.nb2 == 2 && !sys;                    // ... two blocks each (up to 8 192 particles: the reference's default 5 000): gather_totals<2>
+#else
+    constexpr bool rows_direct = false, rows_two = false;       // (the default-run unit is launched with gatherers only: launch2.hpp)
+#endif
     // rides: this stage's correction row was formed in front of its begin, behind the previous stage's mutation row (k3_rides)
     bool rides = false;
 #ifdef SMCMI_K3_CH2
@@ -1723,10 +1788,10 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             sto[T3 + tid] = like; sto[2 * T3 + tid] = lprior; sto[3 * T3 + tid] = like_prev; sto[4 * T3 + tid] = acc_val;
 #if (K3HO) & K3H_REDRAW
             const int bad = k3_select_inside<D, !ALPHA1>(sa.sel, cl.buf[0], cl.n, cl.R, g.N, g.V * g.nb1, g.V, rowi, i, beg, end, tag, n, ma.seed, ma.gid0, sa.g_cm + K3_RPAR(n), sa.to, &s_to, s_tot, s_vt, s_sw,
-                                                red, z_park, stx, sto, po.shift, (sa.prof && writer && n == sa.prof_stage) ? sa.gprof + PROF2_SEL : nullptr, rows_direct, rows_two, db0);
+                                                red, z_park, stx, sto, po.shift, K3_PROF((sa.prof && writer && n == sa.prof_stage) ? sa.gprof + PROF2_SEL : nullptr), rows_direct, rows_two, db0);
 #else
             const int bad = k3_select_inside<D>(sa.sel, cl.buf[0], cl.n, cl.R, g.N, g.V * g.nb1, g.V, rowi, i, beg, end, tag, n, ma.seed, ma.gid0, sa.g_cm + K3_RPAR(n), sa.to, &s_to, s_tot, s_vt, s_sw,
-                                                red, z_park, stx, sto, po.shift, (sa.prof && writer && n == sa.prof_stage) ? sa.gprof + PROF2_SEL : nullptr, rows_direct, rows_two);
+                                                red, z_park, stx, sto, po.shift, K3_PROF((sa.prof && writer && n == sa.prof_stage) ? sa.gprof + PROF2_SEL : nullptr), rows_direct, rows_two);
 #endif
             if (bad) { timed_out = true; break; }
 #pragma unroll
@@ -1777,9 +1842,9 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             // what this stage's shuffle wavefront wrote)
             if (!(((FAST & A1F_FUSE) != 0 && nb == 1 && !((SMCMI_FUSE_VARIANT) & 8))
                       ? proposal2_fused<12, D>(s_tot + 2, po.shift, D, nf, po.c * s_a.bg.cfac, P, &s_fail, T3, entered,
-                                               (sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr)
+                                               K3_PROF((sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr))
                       : proposal2<12, FAST>(s_tot + 2, po.shift, D, nf, nb, po.c * s_a.bg.cfac, ma.seed, (unsigned)n, P, &s_fail, T3, jx_pre, nullptr,
-                           (sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr))) {
+                           K3_PROF((sa.prof && writer && n == sa.prof_stage) ? sa.prof + 30 : nullptr)))) {
                 // PosDefException aborts the run (mutation.jl:81).  The gatherers build no proposal and would wait for mutation rows that
                 // never come: the writer raises the waits' abort word (every bounded wait polls it), so they leave at once
                 if (writer && tid == 0) {
@@ -1879,5 +1944,8 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
     }
     k3_leave_note(sa, ctl);
 }
+#ifdef SMCMI_K3_RUN
+}  // namespace defrun
+#endif
 
 }  // namespace smcmi

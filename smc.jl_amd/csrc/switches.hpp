@@ -15,7 +15,8 @@ struct Switches {
     OptInt e2_nb1;                  // SMCMI_E2_NB1=<n>: correction rows per virtual shard
     int e2_helpers = 1;             // SMCMI_E2_HELPERS: 0 = k2_begin / k2_prepare as launches
     int seg_select = 1;             // SMCMI_SEG_SELECT: 0 = a segment leaves at a stage that must resample
-    int run_prologue = 1;           // SMCMI_RUN_PROLOGUE: 0 = a fresh single-handle run starts and ends with the copies and launches it used to
+    int k3_general = 0;             // SMCMI_K3_GENERAL: 1 = the segment kernel's general unit where the default-run unit would run (launch2.hpp)
+    int run_prologue = 1;          // SMCMI_RUN_PROLOGUE: 0 = a fresh single-handle run starts and ends with the copies and launches it used to
     double seg_timeout_ms = 0.0;    // SMCMI_SEG_TIMEOUT_MS: <= 0 = the driver's bound (200 ms, 1 s across handles)
     // ---- hand-over transport: read at every run (per_run)
     int mailbox = -1;               // SMCMI_MAILBOX: -1 default, 0 off, 1 on, 2 also with one rank
@@ -46,7 +47,7 @@ struct Switches {
         integer("SMCMI_ENGINE", &s.engine); integer("SMCMI_ENGINE3", &s.engine3);
         s.e2_reduced = getenv("SMCMI_E2_REDUCED") != nullptr;
         opt("SMCMI_E2_NB1", &s.e2_nb1); integer("SMCMI_E2_HELPERS", &s.e2_helpers); integer("SMCMI_SEG_SELECT", &s.seg_select);
-        integer("SMCMI_RUN_PROLOGUE", &s.run_prologue);
+        integer("SMCMI_RUN_PROLOGUE", &s.run_prologue); integer("SMCMI_K3_GENERAL", &s.k3_general);
         if (const char *v = getenv("SMCMI_SEG_TIMEOUT_MS")) s.seg_timeout_ms = atof(v);
         integer("SMCMI_NO_PREDICTOR", &s.no_predictor); integer("SMCMI_NO_SELECT_PREDICT", &s.no_select_predict);
         integer("SMCMI_SHIFT_LAG", &s.shift_lag); integer("SMCMI_CENTER", &s.center); integer("SMCMI_FIXED_NO_SELECT", &s.fixed_no_select);

@@ -158,6 +158,7 @@ SYMBOLS = [
     ("smcmi_mailbox_import", C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     ("smcmi_mailbox_selftest", C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("smcmi_mailbox_active", C.c_int, [_H, C.POINTER(C.c_int32)]),
+    ("smcmi_segment_unit", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("smcmi_run_group", C.c_int, [C.POINTER(_H), C.c_int32, C.POINTER(RunConfig), C.POINTER(Result)]),
     ("smcmi_run_ensemble", C.c_int, [C.POINTER(_H), C.c_int32, C.POINTER(RunConfig), C.POINTER(Result), ip]),      # res, status: n entries each
     ("smcmi_weighted_quantiles", C.c_int, [_H, ip, C.c_int32, dp, C.c_int32, dp]),

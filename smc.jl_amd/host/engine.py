@@ -508,6 +508,12 @@ class Engine:
         self._checked(self._L.smcmi_mailbox_active(self._h, C.byref(a)))
         return bool(a.value)
 
+    def segment_unit(self):
+        """Which unit's segment kernel the last segment launch ran: 0 none yet, 1 the default-run unit, 2 any other (include/smcmi.h)."""
+        u = C.c_int32(0)
+        self._checked(self._L.smcmi_segment_unit(self._h, C.byref(u)))
+        return int(u.value)
+
     def run_sharded(self, n_blocks=1, n_mh_steps=1, lam=2.1, n_phi=300, resampling_method="systematic", threshold_ratio=0.5,
                     c=0.5, alpha=1.0, target=0.25, use_fixed_schedule=True, tempering_target=0.97, prior_weight=0.0,
                     log_prob_old_data=0.0, solver_passes=0, phi_rtol=0.0, initial_ess=0.0, use_graph=0, stop_after_stage=0,

@@ -4,7 +4,14 @@
 The worker loop of k3_segment (csrc/stage3.hpp) reads the shader clock at every K3_STAMP: an `s_memtime` whose value the next
 `global_store_dwordx2 ... offset:<8 * slot>` puts into the stamp buffer.  This tool takes the device assembly of an inst3 unit
 (`hipcc -S --cuda-device-only` with the Makefile's flags of the unit), finds one kernel in it, cuts the kernel's text at those clock reads
-and counts the instructions between two consecutive ones by mnemonic prefix:
+and counts the instructions between two consecutive ones by mnemonic prefix.  The α = 1, two-hand-over, one-handle, one-chunk kernel has two
+units (csrc/stage3.hpp SMCMI_K3_RUN), told apart by the name prefix:
+
+  _ZN5smcmi10k3_segmentILi10ELb1ELb0E         the general unit (inst3g_d10: -DSMCMI_INST3_D=10 -DSMCMI_INST3_A=1 -DSMCMI_INST3_R=0)
+  _ZN5smcmi6defrun10k3_segmentILi10ELb1ELb0E  the default-run unit (inst3_d10: the same with -DSMCMI_INST3_U=1) - it has no stamps to cut at
+                                              unless it is compiled with -DSMCMI_K3_KEEP=1 (the development build: VARIANT_FLAGS)
+
+Columns:
 
   valu     every v_* instruction
   select   v_cndmask*
