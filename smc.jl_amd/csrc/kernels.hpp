@@ -93,6 +93,46 @@ __device__ inline double xor_add(double x) {         // x + (x of lane ^ DIST)
     else return x + fetch_xor<DIST>(x);
 }
 
+// fmax(x, x of lane ^ DIST) without the LDS crossbar: what one round of `x = fmax(x, __shfl_xor(x, DIST, 64))` gives, bit for bit.  The two
+// operands of the maximum are the same two values; for DIST >= 16 the swap hands them over in either order (the lower half / the even rows
+// hold their own value first, the others their partner's), and the hardware's maximum of two non-NaN values does not depend on the order
+// (+0 above -0 either way).  fmax itself quiets a signalling NaN and returns the other operand of a quiet one, as v_max_f64 does: the raw
+// instruction, so no canonicalising copy of either operand in front of it.
+__device__ inline double vmax_f64(double a, double b) {
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+template <int DIST>
+__device__ inline double xor_max(double x) {
+    if constexpr (DIST >= 16) {
+        static_assert(DIST == 16 || DIST == 32, "row / half-wave exchanges only");
+        const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+        if constexpr (DIST == 32) {
+            const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+            const auto r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+            return vmax_f64(__hiloint2double((int)r1[0], (int)r0[0]), __hiloint2double((int)r1[1], (int)r0[1]));
+        } else {
+            const auto r0 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+            const auto r1 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+            return vmax_f64(__hiloint2double((int)r1[0], (int)r0[0]), __hiloint2double((int)r1[1], (int)r0[1]));
+        }
+    } else if constexpr (DIST == 4) return vmax_f64(x, fetch_xor<4>(x));
+    else {
+        // (every lane of the row reads a lane of the row: no lane keeps its destination's old value, so the move needs no copy of x in
+        // front of it - bound_ctrl with a constant `old` tells the compiler so)
+        constexpr int CTRL = DIST == 1 ? 0xB1 : (DIST == 2 ? 0x4E : 0x128);      // fetch_xor's quad_perm [1,0,3,2] / [2,3,0,1] / row_ror:8
+        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xf, 0xf, true);
+        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xf, 0xf, true);
+        return vmax_f64(x, __hiloint2double(hi, lo));
+    }
+}
+// the wavefront's maximum in every lane: the rounds 32, 16, 8, 4, 2, 1 of the __shfl_xor loop, in that order
+__device__ inline double wave_max_swap(double x) {
+    x = xor_max<32>(x); x = xor_max<16>(x); x = xor_max<8>(x); x = xor_max<4>(x); x = xor_max<2>(x); x = xor_max<1>(x);
+    return x;
+}
+
 template <int HALF, int DIST>
 struct Butterfly {
     template <int M>

@@ -2024,14 +2024,19 @@ SMCMI_FP_CONTRACT
 // One mutation block's row for the next stage's begin (energy power sums on adaptive schedules, Σ accept, energy maximum) from the
 // particles' post-mutation values; scratch: T / 64 * ES doubles of LDS (the likelihood data is dead by now), red: 8 doubles.
 // coh: the row is totalled inside this launch (Tail2 / stage3.hpp).  All threads call; starts and ends with a barrier.
-template <int T, class ST>
+// SWAPMAX (the segment kernel's default-run unit, stage3.hpp K3H_EMAX): the wavefront's energy maximum through the lane swaps and DPP moves
+// the sums take (kernels.hpp wave_max_swap) - the same six rounds on the same operands, no LDS round trip
+template <int T, bool SWAPMAX = false, class ST>
 __device__ inline void k2_mut_row_f(bool adaptive, double like, double like_prev, double w_part, double acc_val, double e_center, bool live,
                                     bool rs, double *scratch, double *red, ST store, double e_base) {
     const int tid = threadIdx.x;
     __syncthreads();
     double em = energy_or_ninf(like, e_base, rs ? 1.0 : w_part, live);      // (e_base: kernels.hpp energy_base - like_prev itself unless a prior weight is set)
+    if constexpr (SWAPMAX) em = wave_max_swap(em);
+    else {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) em = fmax(em, __shfl_xor(em, off, 64));
+        for (int off = 32; off >= 1; off >>= 1) em = fmax(em, __shfl_xor(em, off, 64));
+    }
     __shared__ double emx[T / 64];
     if ((tid & 63) == 0) emx[tid >> 6] = em;
     if (adaptive) {

@@ -400,16 +400,20 @@ __device__ inline bool gather_totals_pair(const unsigned long long *tbl_m, unsig
 // ... and the per-particle phases' vector instructions the result does not need (same rule: no operation on a live value, or its order, moves)
 #define K3H_DEAD 16               // α = 1: the correction row's sums without the `live` select - a dead lane's operands are +0.0 (k2_cm_row_one DEADZERO)
 #define K3H_LIVE 32               // α = 1: the worker's `live` mask from a flag in a vector register where it is used (one v_cmp), not carried across the loop in spilled scalars
+// ... of the DEFAULT-RUN unit alone (SMCMI_K3_RUN; the general unit of the same kernel keeps its text)
+#define K3H_EMAX 64               // the mutation row's energy maximum through lane swaps and DPP moves, not six LDS-crossbar rounds (k2_mut_row_f SWAPMAX)
 #ifndef SMCMI_K3HO
-#define SMCMI_K3HO (K3H_FETCH | K3H_SW | K3H_REDRAW | K3H_GATHER | K3H_DEAD | K3H_LIVE)
+#define SMCMI_K3HO (K3H_FETCH | K3H_SW | K3H_REDRAW | K3H_GATHER | K3H_DEAD | K3H_LIVE | K3H_EMAX)
 #endif
-#if defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1 && SMCMI_INST3_A != 0
+#if defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1 && SMCMI_INST3_A != 0 && defined(SMCMI_K3_RUN)
 #define K3HO (SMCMI_K3HO)
+#elif defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1 && SMCMI_INST3_A != 0
+#define K3HO ((SMCMI_K3HO) & ~K3H_EMAX)
 #elif defined(SMCMI_INST3_D) && SMCMI_INST3_R == 0 && SMCMI_INST3_S == 0 && SMCMI_INST3_C == 1
 // (the mixture kernel: with the redraw inside k3_select_inside its scratch grows from 64 to 80 bytes per lane at n_para 10, past the bound
 // tests/test_abi_cpu.py holds it to; its redraw stays where it was.  K3H_DEAD does not reach it - its row goes through accumulators - and
 // K3H_LIVE left its headline where it was, 8.24 ms per step either way: the mixture units keep their parent's device code)
-#define K3HO ((SMCMI_K3HO) & ~(K3H_REDRAW | K3H_DEAD | K3H_LIVE))
+#define K3HO ((SMCMI_K3HO) & ~(K3H_REDRAW | K3H_DEAD | K3H_LIVE | K3H_EMAX))
 #else
 #define K3HO 0
 #endif
@@ -1888,7 +1892,7 @@ __global__ void __launch_bounds__(T3, SMCMI_K3_WAVES) k3_segment(CloudPtrs cl, D
             double *plain = ma.rows_mut + (long long)rowi * RMUT;      // (the launch after this one totals the last stage's rows from here)
             unsigned long long *my_mut = sa.g_mut + K3_RPAR(n) + (long long)rowi * RMUT * 2;
             K3_LIVE_ROW_DECL;
-            k2_mut_row_f<T3>(ma.adaptive != 0, like, like_prev, K3_LIVE_ROW ? Wt : 0.0, K3_LIVE_ROW ? acc_val : 0.0, e_center, K3_LIVE_ROW, rs != 0, red, L.red,
+            k2_mut_row_f<T3, ((K3HO) & K3H_EMAX) != 0>(ma.adaptive != 0, like, like_prev, K3_LIVE_ROW ? Wt : 0.0, K3_LIVE_ROW ? acc_val : 0.0, e_center, K3_LIVE_ROW, rs != 0, red, L.red,
                              [&](int idx, double val) { if (K3_HAS) { gran_store(my_mut + idx * 2, val, tag); plain[idx] = val; } },
                              energy_base(like_prev, rp.pw, rp.logp_old));
             if (K3_HAS && tid == RMUT - 1) gran_store(my_mut + tid * 2, 0.0, tag);                  // (column 33 is unused)
